@@ -11,6 +11,14 @@ Viterbi, energy dispersal, FIB CRC, superframe filter with Reed-Solomon) over on
 synthetic 2.048 Msps complex-float IQ that is already resident in HBM (BASELINE.json config "1xMI355X: batch of 256 synthetic Mode-I
 ensembles"; welle_io_amd/workload.py builds signal and handle, tests/test_gpu_bench_config.py checks exactly this configuration
 against the oracle).  value = ensembles decoded in real time (x real-time) summed over all GPUs = N*B*F*0.096 s / step time.
+
+A plain run does only what that figure needs: signal and handle, warm-up, the K timed steps, the line (with the FFT-stage and Viterbi
+rooflines derived from the timed steps' own kernel times).  `--full` adds everything measured or checked beside it, after the timed
+region: the CPU baseline and the parity check of this run against CPU receivers (every rank's own shard with N > 1), the measured
+device-copy rate, the other pipelined schedules, the bulk MSC drain and the side legs (heterogeneous multiplex, independent
+ensembles, drift, low SNR, short batches, facade, host u8).  `--dump-outputs DIR` writes what the last timed step returned to its
+caller (decoded FIBs, their CRC flags, the superframe filter's totals) as DIR/<name>.npy; the signal is seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -474,6 +482,30 @@ def _extra(cmd, env_extra, timeout):
         return {"error": "%s: %s" % (type(ex).__name__, ex)}
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, fib, ok, sf, gathered=None):
+    """--dump-outputs: what the last timed step returned to its caller -- fibs [E][F][12][32] (decoded FIB bytes), crc_ok [E][F][12]
+    (their CRC flags) as float32, superframes [B][4] (the superframe filter's totals of this rank's ensembles, capi.superframes_stats) as
+    float64.  With N ranks E = N*B: the FIBs every rank sent to rank 0 (`gathered`), in rank order.  Should fibs + crc_ok exceed the
+    budget, a fixed seeded sample of ensembles is written instead and ensembles.npy names them."""
+    if gathered is not None:
+        fib = np.concatenate([np.asarray(g[0]) for g in gathered]); ok = np.concatenate([np.asarray(g[1]) for g in gathered])
+    fib = np.asarray(fib); ok = np.asarray(ok); sf = np.asarray(sf)
+    os.makedirs(out_dir, exist_ok=True)
+    E = fib.shape[0]
+    row_bytes = 4 * (fib[0].size + ok[0].size)
+    keep = max(1, (DUMP_MAX_BYTES - 8 * sf.size - 4096) // (row_bytes + 8))           # (4096: the four .npy headers)
+    if E > keep:
+        rows = np.sort(np.random.RandomState(0).choice(E, keep, replace=False))
+        fib, ok = fib[rows], ok[rows]
+        np.save(os.path.join(out_dir, "ensembles.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "fibs.npy"), fib.astype(np.float32))
+    np.save(os.path.join(out_dir, "crc_ok.npy"), ok.astype(np.float32))
+    np.save(os.path.join(out_dir, "superframes.npy"), sf.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -482,10 +514,16 @@ def main():
     ap.add_argument("--ensembles", type=int, default=256, help="ensembles per GPU")
     ap.add_argument("--frames", type=int, default=32, help="transmission frames per ensemble and step (round 1 and most of round 2 ran 20; DESIGN.md section 6 has the sweep)")
     ap.add_argument("--cfo-max-hz", type=float, default=60.0, help="per-ensemble carrier frequency offsets are drawn from +-this (small enough for DQPSK to decode from the first frame on, so every ensemble keeps the same frame count; the oscillator cost does not depend on the value)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (and with it the parity check of this run)")
-    ap.add_argument("--no-alt-schedule", action="store_true", help="skip the extra (untimed) pass with the other pipelined schedule")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side measurements behind the timed region (heterogeneous multiplex, single-ensemble facade latency, host-u8 PCIe-inclusive rate)")
+    ap.add_argument("--full", action="store_true", help="also run what is measured or checked beside the headline, after the timed region: CPU baseline + parity check, measured copy rate, other schedules, side legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (FIBs, CRC flags, superframe totals) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (and with it the parity check of this run)")
+    ap.add_argument("--no-alt-schedule", action="store_true", help="with --full: skip the extra (untimed) pass with the other pipelined schedule")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the side measurements behind the timed region (heterogeneous multiplex, single-ensemble facade latency, host-u8 PCIe-inclusive rate)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:                                      # a plain run: the headline only
+        args.no_cpu_baseline = args.no_alt_schedule = args.no_extras = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # not under a launcher: start the N ranks ourselves, one process per GPU; rank 0's JSON line is this process's output
@@ -590,7 +628,7 @@ def main():
     logs = {e: dict(fib=[], ok=[], msc=[[] for _ in PARITY_SUBCH]) for e in check}
     for W in range(max(2, args.warmup)):
         fib, ok, sf = step()
-        if check and (world > 1 or not args.no_cpu_baseline) and W * F < 64:           # (the CPU receivers keep their first 64 frames for the comparison)
+        if check and ((world > 1 and args.full) or not args.no_cpu_baseline) and W * F < 64:           # (the CPU receivers keep their first 64 frames for the comparison)
             info = dev.frame_info()
             mscs = [dev.msc(i) for i in PARITY_SUBCH]
             lfib, lok = (fib, ok) if dist is None else dev.fibs()        # (with ranks, `fib` is the gathered set and only rank 0 has it)
@@ -622,7 +660,7 @@ def main():
     dev_sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        fib_last, ok_last, sf_last = step()
         for k, v in dev.stage_times().items():
             stage_acc[k] = stage_acc.get(k, 0.0) + v
     dev_sync()
@@ -638,11 +676,14 @@ def main():
         td_ = torch.zeros(world, device=tt.device, dtype=torch.float64); td_[rank] = stage_acc.get("demod", 0.0) / args.steps
         dist.all_reduce(td_, op=dist.ReduceOp.SUM)
         demod_ms_ranks = [float(v) for v in td_.cpu()]
+    if args.dump_outputs and rank == 0:                    # (before anything else touches the handle: fib / ok are views until the next process())
+        dump_outputs(args.dump_outputs, fib_last, ok_last, sf_last, gatherer.views if gatherer is not None else None)
 
-    # ---- multi-rank runs: every rank proves ITS shard (outside the timed region): the first and the last ensemble of the shard through
-    # the oracle on this host, FIBs + CRC flags + MSC bytes of three sub-channels from the very first frame on; the verdicts are summed
+    # ---- multi-rank runs with --full: every rank proves ITS shard (outside the timed region): the first and the last ensemble of the
+    # shard through the oracle on this host, FIBs + CRC flags + MSC bytes of three sub-channels from the very first frame on; the verdicts
+    # are summed
     ranks_ok = None; rank_err = None
-    if world > 1:
+    if world > 1 and args.full:
         import tempfile
         flag = 0
         try:
@@ -748,26 +789,27 @@ def main():
         # what a plain device-to-device copy moves on this box (read + write), for scale next to the 8 TB/s specification the fraction is
         # taken against ("measure the denominator"); never used as `peak`.  The library's own float4 grid-stride copy
         # (dabphy_time_copy, the recipe MI355X_MICROARCH.md quotes 6.29 TB/s for; tools/ubench/copy_f4.hip sweeps it), 2 GiB in + 2 GiB out
-        # per pass; torch's copy_ beside it (round 3's denominator: it flattered)
-        try:
-            if emu:
-                raise RuntimeError("emulator run: no copy measured")
-            sweep = {k: dev.time_copy(2 << 30, k, 5) for k in (2, 4, 8, 16)}
-            cg = max(sweep.values())
-            line["roofline"]["measured_copy_GBps"] = cg
-            line["roofline"]["frac_of_achievable"] = ach / cg
-            line["roofline"]["measured_copy_note"] = "float4 grid-stride device copy of 2 GiB (read + write counted), best of 2 / 4 / 8 / 16 work-groups per CU (%s), after this run's timed region on the same device (dabphy_time_copy; tools/ubench/copy_f4.hip is the full sweep, profiles/r04_copy_f4.txt)" % ", ".join("%d: %.0f" % kv for kv in sorted(sweep.items()))
-            src = iq[: max(1, B // 2)]; dst = torch.empty_like(src)
-            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-            dst.copy_(src); torch.cuda.synchronize()
-            e0.record()
-            for _ in range(3):
-                dst.copy_(src)
-            e1.record(); torch.cuda.synchronize()
-            line["roofline"]["torch_copy_GBps"] = 3 * 2 * src.numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-            del dst
-        except Exception as ex:
-            line["roofline"]["measured_copy_error"] = "%s: %s" % (type(ex).__name__, ex)
+        # per pass; torch's copy_ beside it (round 3's denominator: it flattered); --full only (passes of their own)
+        if args.full:
+            try:
+                if emu:
+                    raise RuntimeError("emulator run: no copy measured")
+                sweep = {k: dev.time_copy(2 << 30, k, 5) for k in (2, 4, 8, 16)}
+                cg = max(sweep.values())
+                line["roofline"]["measured_copy_GBps"] = cg
+                line["roofline"]["frac_of_achievable"] = ach / cg
+                line["roofline"]["measured_copy_note"] = "float4 grid-stride device copy of 2 GiB (read + write counted), best of 2 / 4 / 8 / 16 work-groups per CU (%s), after this run's timed region on the same device (dabphy_time_copy; tools/ubench/copy_f4.hip is the full sweep, profiles/r04_copy_f4.txt)" % ", ".join("%d: %.0f" % kv for kv in sorted(sweep.items()))
+                src = iq[: max(1, B // 2)]; dst = torch.empty_like(src)
+                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+                dst.copy_(src); torch.cuda.synchronize()
+                e0.record()
+                for _ in range(3):
+                    dst.copy_(src)
+                e1.record(); torch.cuda.synchronize()
+                line["roofline"]["torch_copy_GBps"] = 3 * 2 * src.numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+                del dst
+            except Exception as ex:
+                line["roofline"]["measured_copy_error"] = "%s: %s" % (type(ex).__name__, ex)
         if world == 1 and not args.no_extras:
             try:
                 line["msc_drain"] = msc_drain_leg(dev, torch, B, F, args.steps, B * len(subchs))
@@ -808,7 +850,7 @@ def main():
             if world == 1:
                 line["parity_check"] = pc
                 line["parity_check"].update(ranks_ok=1, ranks=1)
-        if world > 1:
+        if world > 1 and args.full:
             line["parity_check"] = {"ranks_ok": ranks_ok, "ranks": world, "per_rank": "ensembles %s of the rank's own shard: FIBs + CRC flags + MSC bytes of sub-channels %s from the first frame on vs the oracle (C restatement) on the same rows, outside the timed region" % (check, list(PARITY_SUBCH)),
                                     "fib_equal": ranks_ok == world, "msc_equal": ranks_ok == world, "rank0_error": rank_err}
             if not args.no_cpu_baseline:

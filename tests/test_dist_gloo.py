@@ -67,7 +67,7 @@ def test_eight_ranks_of_bench_py_over_gloo(emu):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, DABPHY_BENCH_EMU="1", OMP_NUM_THREADS="1", DABPHY_PIPELINE="1", DABPHY_SP_MAX_CW="0")      # (the execution model runs the state-parallel kernels a wavefront at a time: lane per code word here, as in tests/conftest.py)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "7", "--ensembles", "2", "--frames", "2", "--no-cpu-baseline"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "7", "--ensembles", "2", "--frames", "2", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

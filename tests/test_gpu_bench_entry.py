@@ -23,7 +23,7 @@ def run_bench(args, env_extra=None, timeout=900):
 
 
 def test_single_gpu_line_and_parity_leg(gpu):
-    j = run_bench(["--gpus", "1", "--steps", "2", "--warmup", "2", "--ensembles", "8", "--frames", "10", "--no-alt-schedule"])
+    j = run_bench(["--full", "--gpus", "1", "--steps", "2", "--warmup", "2", "--ensembles", "8", "--frames", "10", "--no-alt-schedule"])
     assert j["n_gpus"] == 1 and j["rccl_ranks"] == 0 and j["value"] > 0 and j["higher_is_better"] is True
     for k in ("roofline", "roofline_viterbi", "cpu_baseline", "parity_check", "stages_ms"):
         assert k in j, k
@@ -70,7 +70,7 @@ def test_gpus_2_starts_its_ranks(gpu):
     env = dict(env, **{k: "" for k in ()})
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         os.environ.pop(k, None)
-    j = run_bench(["--gpus", "2", "--steps", "1", "--ensembles", "4", "--frames", "10", "--no-alt-schedule"], env)
+    j = run_bench(["--full", "--gpus", "2", "--steps", "1", "--ensembles", "4", "--frames", "10", "--no-alt-schedule"], env)
     assert j["n_gpus"] == 2 and j["config"]["ensembles_per_gpu"] == 4
     assert j["rccl_ranks"] == (2 if torch.cuda.device_count() >= 2 else 0)
     # the multi-rank line is as complete as the single-GPU one: roofline of the slowest rank (per-rank kernel times beside it) and the
@@ -82,3 +82,21 @@ def test_gpus_2_starts_its_ranks(gpu):
     assert j["parity_check"]["ranks_ok"] == 2 and j["parity_check"]["fib_equal"] and j["parity_check"]["msc_equal"], j["parity_check"]
     # (round 5 also compared the baseline with a one-rank run of the same configuration: dropped from the device suite in round 6 -- 20 s for a
     # figure that moves by 10 % with the host's other load)
+
+
+def test_plain_line_and_dumped_outputs(gpu, tmp_path):
+    """a plain run (no --full) is the headline alone; --dump-outputs writes the last timed step's outputs, the same from run to run"""
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--ensembles", "8", "--frames", "10"]
+    runs = [run_bench(args + ["--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    for j in runs:
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and abs(j["value"] - 8 * 10 * 0.096 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+        for k in ("metric", "unit", "higher_is_better", "dtype", "roofline", "stages_ms"):
+            assert k in j, k
+        for k in ("cpu_baseline", "parity_check", "extras", "facade", "host_u8", "msc_drain", "alt_schedules"):
+            assert k not in j, k
+        assert "measured_copy_GBps" not in j["roofline"]
+    for name, shape, dtype in (("fibs", (8, 10, 12, 32), np.float32), ("crc_ok", (8, 10, 12), np.float32), ("superframes", (8, 4), np.float64)):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.shape == shape and a.dtype == dtype and np.array_equal(a, b), name
+    assert np.load(tmp_path / "a" / "crc_ok.npy").all()

@@ -24,7 +24,7 @@ timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_LDS_BANK
 hipcc --offload-arch=gfx950 -O3 tools/ubench/valu_rate.hip -o /tmp/valu_rate && timeout 120 /tmp/valu_rate > $O/valu_rate.txt 2>&1
 # the drift leg (every ensemble its own sampling-clock offset: the find chain) under the kernel tracer, on its own
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o drift -- python tools/bench_channel.py drift > $O/drift.log 2>&1
-timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err
 # (gpurun copies at most 64 MiB back: the per-dispatch traces of the long passes stay on the box, the statistics are what is kept)
 find $O -name "*kernel_trace.csv" -size +4M -delete; find $O -name "*.db" -delete; find $O -name "*.pftrace" -delete
 tail -n 2 $O/*.log | cut -c1-300
