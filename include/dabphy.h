@@ -58,7 +58,8 @@ typedef enum {
 #define DABPHY_ABI_VERSION 6u
 uint32_t dabphy_abi_version(void);
 typedef enum { DABPHY_STRUCT_CONFIG = 0, DABPHY_STRUCT_FRAME_INFO = 1, DABPHY_STRUCT_SF_EVENT = 2, DABPHY_STRUCT_SUBCHANNEL = 3,
-               DABPHY_STRUCT_PROTECTION = 4, DABPHY_STRUCT_TII_MEASUREMENT = 5, DABPHY_STRUCT_MSC_DESC = 6 } dabphy_struct_id;
+               DABPHY_STRUCT_PROTECTION = 4, DABPHY_STRUCT_TII_MEASUREMENT = 5, DABPHY_STRUCT_MSC_DESC = 6,
+               DABPHY_STRUCT_MP2_EVENT = 7 } dabphy_struct_id;
 size_t dabphy_struct_size(int32_t which);      /* 0 for an unknown id */
 
 /* RadioReceiverOptions (src/backend/radio-receiver-options.h:66-84) + batch geometry */
@@ -436,6 +437,57 @@ int dabphy_superframes_stats(dabphy_handle* h, int32_t* stats);
  * the sub-channel lists, dabphy_reset and switching the mode run or drop what is pending first.
  * on = 0: dabphy_superframes_stats runs the pass when it is called. */
 int dabphy_set_auto_superframes(dabphy_handle* h, int32_t on);
+
+/* ---- Classic DAB (MPEG-1/2 Layer II, "MP2") services: the frame check MP2Decoder::Feed makes before it decodes (dab_decoder.cpp:114-250)
+ * -- mpg123's frame parser in feed mode (sync, look-ahead on the first frame, resync byte by byte) and the MP2 CRC over header, bit
+ * allocation and ScFSI -- on the device, one Feed per logical frame as DecoderAdapter::addtoFrame calls it.  No audio is decoded.
+ *
+ * dabphy_set_audio_kinds_ensemble   the audio kind of every position of ONE ensemble's list (n = the list's length as last set):
+ *                                   DABPHY_AUDIO_DABPLUS (the default) or DABPHY_AUDIO_MP2.  Takes effect with the next dabphy_process,
+ *                                   like the list itself.  A new list (dabphy_set_subchannels[_ensemble]) resets every position of it
+ *                                   to DABPHY_AUDIO_DABPLUS: set the kinds AFTER the list.  A service that stays in the list and stays
+ *                                   MP2 keeps its parser state (bytes not yet consumed, headers, output format); one that becomes MP2
+ *                                   starts fresh.  MP2 positions are left out of the DAB+ filter (dabphy_superframes_stats and its
+ *                                   automatic pass; dabphy_superframes[_ensemble] on them: DABPHY_ERR_INVALID).  A caller that sets no
+ *                                   kinds gets exactly what it got before.
+ * The MP2 pass runs at most once per batch, over every MP2 service of every ensemble; the first of dabphy_mp2_frames_ensemble /
+ * dabphy_mp2_stats after a dabphy_process runs it (or dabphy_process itself, with dabphy_set_auto_mp2(h, 1)), the others read its
+ * results.  In exact batch mode a replayed batch is checked once, on its final bytes.
+ *
+ * Exactness: every frame before first_unverified is what the reference reports.  Paths of mpg123 that are not restated -- free
+ * format, a header of another layer or of a sampling rate without an output format (the reference throws), a Frankenstein stream,
+ * ID3 / TAG / APE / RIFF tags -- end the claim for that service from the logical frame where they are met; it stays unverified until
+ * its list position is set to MP2 afresh or dabphy_reset.  DESIGN.md section 4.7. */
+#define DABPHY_AUDIO_DABPLUS 0
+#define DABPHY_AUDIO_MP2 1
+int dabphy_set_audio_kinds_ensemble(dabphy_handle* h, uint32_t ensemble, const int32_t* kinds, uint32_t n);
+typedef struct {
+    int32_t frame;                       /* logical frame of the batch (0 .. 4*n_frames-1) whose Feed returned this MP2 frame */
+    uint32_t header;                     /* the 32-bit MPEG header */
+    int64_t offset;                      /* of the header in the service's byte stream since it became MP2 (unit entry: since frames[0]) */
+    uint8_t crc_ok;                      /* CheckCRC passed (0: an AudioError) */
+    uint8_t new_format;                  /* mpg123_framebyframe_next said MPG123_NEW_FORMAT (ProcessFormat ran) */
+    uint8_t scf_crc_len;                 /* 2 or 4, as ProcessFormat set it */
+    uint8_t fpad[2];                     /* the F-PAD bytes ProcessPAD receives */
+    uint8_t pad_[3];
+} dabphy_mp2_event;
+/* ... of sub-channel subch_index of ONE ensemble (an MP2 position; else DABPHY_ERR_INVALID), over the last batch:
+ *   events           [cap]: one record per frame the reference's decoder returned, in order (at most 2 per logical frame + 8 are kept)
+ *   n_events         frames returned (may exceed what was stored)
+ *   frame_errors     [4 * n_frames]: what onFrameErrors reports after each logical frame (0 for rows the batch did not decode)
+ *   first_unverified logical frame of the batch from which equality with the reference is not claimed, -1 */
+int dabphy_mp2_frames_ensemble(dabphy_handle* h, uint32_t ensemble, uint32_t subch_index, dabphy_mp2_event* events, int32_t cap,
+                               int32_t* n_events, int32_t* frame_errors, int32_t* first_unverified);
+/* totals of every MP2 service: stats [n_ensembles][4] = frames checked, CRC failures, bytes skipped in resync, unverified logical frames */
+int dabphy_mp2_stats(dabphy_handle* h, int32_t* stats);
+/* on = 1: every following dabphy_process queues the MP2 pass itself, behind the decoders (dabphy_mp2_stats then fetches its totals);
+ * on = 0: the first getter after a batch runs it. */
+int dabphy_set_auto_mp2(dabphy_handle* h, int32_t on);
+/* Unit entry: the same kernel on host-supplied logical frames, each stream from a fresh state.
+ *   frames [n_streams][n_frames][frame_len] (frame_len <= 2048), events [n_streams][cap], n_events [n_streams],
+ *   frame_errors [n_streams][n_frames], first_unverified [n_streams]; event.frame = index of the logical frame. */
+int dabphy_mp2_check(dabphy_handle* h, const uint8_t* frames, uint32_t n_streams, uint32_t n_frames, uint32_t frame_len,
+                     dabphy_mp2_event* events, int32_t cap, int32_t* n_events, int32_t* frame_errors, int32_t* first_unverified);
 
 /* ---- TIIDecoder (tii-decoder.cpp:189-383), fed by OFDMProcessor::run with the PRS and the trailing NULL symbol of every
  * frame (ofdm-processor.cpp:381-386,462-466) when RadioReceiverOptions::decodeTII is set (radio-receiver-options.h:75; welle-cli

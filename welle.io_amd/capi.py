@@ -36,6 +36,9 @@ SF_EVENT_DTYPE = np.dtype([("cif", "<i4"), ("corrected", "<i4"), ("uncorrectable
 
 FRAME_INFO_RAW = np.dtype({"names": ["sample_pos", "frame_no", "start_index", "valid", "fine_corrector", "coarse_corrector", "snr"],
                            "formats": ["<i8", "<i8", "<i4", "<i4", "<i4", "<i4", "<f4"], "offsets": [0, 8, 16, 20, 24, 28, 32], "itemsize": 40})      # dabphy_frame_info
+MP2_EVENT_DTYPE = np.dtype([("frame", "<i4"), ("header", "<u4"), ("offset", "<i8"), ("crc_ok", "u1"), ("new_format", "u1"), ("scf_crc_len", "u1"),
+                            ("fpad", "u1", 2), ("pad_", "u1", 3)])      # dabphy_mp2_event
+AUDIO_DABPLUS, AUDIO_MP2 = 0, 1                                           # dabphy_set_audio_kinds_ensemble
 MSC_DESC_DTYPE = np.dtype([("ensemble", "<u4"), ("subch_index", "<u4"), ("row_bytes", "<u4"), ("first_valid", "<i4"), ("n_rows", "<i4"), ("subch_id", "<u4"), ("offset", "<u8")])
 
 
@@ -323,6 +326,49 @@ class DabPhy:
         sf = np.zeros((4 * F // 5 + 1, 15 * bitrate), np.uint8)
         self._chk(self.lib.dabphy_superframes_ensemble(self.h, ensemble, idx, _p(ev), C.byref(ne), _p(sf)))
         return ev, ne.value, sf
+
+    # ---- classic DAB (MP2) services
+    def set_audio_kinds_ensemble(self, ensemble, kinds):
+        """AUDIO_DABPLUS / AUDIO_MP2 for every position of ONE ensemble's list (set after the list; takes effect with the next process())"""
+        k = np.ascontiguousarray(kinds, np.int32)
+        self._chk(self.lib.dabphy_set_audio_kinds_ensemble(self.h, ensemble, _p(k), C.c_uint32(len(k))))
+
+    def mp2_frames_ensemble(self, ensemble, idx):
+        """-> (events [n] of MP2_EVENT_DTYPE, n_events, frame_errors [4F], first_unverified) of one ensemble's MP2 sub-channel idx"""
+        F = self._last
+        cap = 8 * F + 8
+        ev = np.zeros(cap, MP2_EVENT_DTYPE); ne = C.c_int32(0); fe = np.zeros(4 * F, np.int32); fu = C.c_int32(0)
+        self._chk(self.lib.dabphy_mp2_frames_ensemble(self.h, ensemble, idx, _p(ev), C.c_int32(cap), C.byref(ne), _p(fe), C.byref(fu)))
+        return ev[:min(ne.value, cap)], ne.value, fe, fu.value
+
+    def mp2_stats(self):
+        """[n_ensembles][4]: frames checked, CRC failures, bytes skipped in resync, unverified logical frames"""
+        st = np.zeros((self.cfg.n_ensembles, 4), np.int32)
+        self._chk(self.lib.dabphy_mp2_stats(self.h, _p(st)))
+        return st
+
+    def set_auto_mp2(self, on=True):
+        self._chk(self.lib.dabphy_set_auto_mp2(self.h, int(on)))
+
+    def mp2_ms(self):
+        """device time of the last MP2 pass run with profiling on"""
+        ms = C.c_float(0)
+        self._chk(self.lib.dabphy_get_mp2_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def mp2_check(self, frames, frame_len, cap=None):
+        """unit entry: frames [n_streams][n_frames * frame_len] (or one stream as bytes) from fresh parsers ->
+        (events per stream (lists of MP2_EVENT_DTYPE arrays), n_events [S], frame_errors [S][n_frames], first_unverified [S])"""
+        if isinstance(frames, (bytes, bytearray)):
+            frames = np.frombuffer(bytes(frames), np.uint8)[None]
+        frames = np.ascontiguousarray(frames, np.uint8)
+        S = frames.shape[0]
+        nf = frames.shape[1] // frame_len
+        frames = np.ascontiguousarray(frames[:, :nf * frame_len])
+        cap = 2 * nf + 8 if cap is None else cap
+        ev = np.zeros((S, max(cap, 1)), MP2_EVENT_DTYPE); ne = np.zeros(S, np.int32); fe = np.zeros((S, nf), np.int32); fu = np.zeros(S, np.int32)
+        self._chk(self.lib.dabphy_mp2_check(self.h, _p(frames), C.c_uint32(S), C.c_uint32(nf), C.c_uint32(frame_len), _p(ev), C.c_int32(cap), _p(ne), _p(fe), _p(fu)))
+        return [ev[s, :min(ne[s], cap)] for s in range(S)], ne, fe, fu
 
     def host_alloc(self, shape, dtype):
         """page-locked numpy array (dabphy_host_alloc); release with host_free(arr)"""

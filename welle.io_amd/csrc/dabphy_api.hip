@@ -16,6 +16,7 @@ size_t dabphy_struct_size(int32_t which)
         case DABPHY_STRUCT_PROTECTION: return sizeof(dabphy_protection);
         case DABPHY_STRUCT_TII_MEASUREMENT: return sizeof(dabphy_tii_measurement);
         case DABPHY_STRUCT_MSC_DESC: return sizeof(dabphy_msc_desc);
+        case DABPHY_STRUCT_MP2_EVENT: return sizeof(dabphy_mp2_event);
     }
     return 0;
 }
@@ -60,7 +61,7 @@ int dabphy_create_v2(const dabphy_config* cfg_in, dabphy_handle** out)
     if (hipSetDevice(cfg->device) != hipSuccess) return DABPHY_ERR_NO_DEVICE;
     dabphy_handle* h = new dabphy_handle();
     h->cfg = *cfg;
-    h->subch_e.resize(cfg->n_ensembles); h->subch_next.resize(cfg->n_ensembles); h->where.resize(cfg->n_ensembles);
+    h->subch_e.resize(cfg->n_ensembles); h->subch_next.resize(cfg->n_ensembles); h->where.resize(cfg->n_ensembles); h->kind_next.resize(cfg->n_ensembles);
     // big batches: fewer reference-symbol transforms; small ones: more work-groups.  (Longer chunks -- 38, 75 symbols -- are 2-3 %
     // faster when the kernel runs alone, dabphy_time_demod, and 1-4 % slower inside the pipelined step: measured, round 2.)
     if (h->cfg.demod_chunk <= 0) h->cfg.demod_chunk = ((int64_t)h->cfg.n_ensembles * h->cfg.max_frames >= 1024) ? 25 : 15;
@@ -197,7 +198,8 @@ int dabphy_create_v2(const dabphy_config* cfg_in, dabphy_handle** out)
 void free_class(dabphy_handle::MscClass& c)
 {
     hipError_t e = hipSuccess;
-    DevBuf* bufs[] = {&c.map, &c.pair_tab, &c.tiles, &c.out, &c.steps[0], &c.steps[1], &c.steps[2], &c.sf_state, &c.sf_snap};
+    DevBuf* bufs[] = {&c.map, &c.pair_tab, &c.tiles, &c.out, &c.steps[0], &c.steps[1], &c.steps[2], &c.sf_state, &c.sf_snap,
+                      &c.dab_run, &c.mp2_run, &c.mp2_state, &c.mp2_snap, &c.mp2_ev, &c.mp2_n, &c.mp2_err, &c.mp2_fu};
     for (DevBuf* b : bufs) if (b->p) { e = hipFree(b->p); b->p = nullptr; b->cap = 0; }
     (void)e;
 }
@@ -254,6 +256,8 @@ void dabphy_destroy(dabphy_handle* h)
     DevBuf* more[] = {&h->s_raw, &h->s_raw2[0], &h->s_raw2[1], &h->s_null, &h->s_iq_own, &h->s_desc2[0], &h->s_desc2[1], &h->s_desc2[2], &h->s_soft, &h->s_cir2[0], &h->s_cir2[1], &h->s_cir2[2], &h->s_con, &h->s_mag, &h->s_snr, &h->s_fib, &h->s_ok, &h->rs_first, &h->rs_result};
     for (DevBuf* b : more) if (b->p) e = hipFree(b->p);
     { DevBuf* sfb[] = {&h->sf_events, &h->sf_count, &h->sf_bytes, &h->sf_stats, &h->sf_gf, &h->sf_accept, &h->sf_run, &h->sf_batch}; for (DevBuf* b : sfb) if (b->p) e = hipFree(b->p); }
+    { DevBuf* mb[] = {&h->mp2_stats, &h->mp2_chk_state, &h->mp2_chk_ev, &h->mp2_chk_n, &h->mp2_chk_err, &h->mp2_chk_fu}; for (DevBuf* b : mb) if (b->p) e = hipFree(b->p); }
+    for (int i = 0; i < 2; i++) if (h->ev_mp2[i]) e = hipEventDestroy(h->ev_mp2[i]);
     { DevBuf* tb[] = {&h->s_hist, &h->tii_rot, &h->tii_rank, &h->tii_pat, &h->tii_err, &h->tii_likely, &h->tii_state, &h->tii_events, &h->tii_nev, &h->tii_ovf}; for (DevBuf* b : tb) if (b->p) e = hipFree(b->p); }
     for (auto& c : h->classes) free_class(c);
     DevBuf* bufs[] = {&h->iq, &h->soft, &h->con, &h->prs_mag, &h->snr, &h->desc, &h->in8, &h->map, &h->vsym, &h->vdec, &h->vout, &h->ok, &h->fsym, &h->fdec};
@@ -447,6 +451,8 @@ int dabphy_set_subchannels(dabphy_handle* h, const dabphy_subchannel* list, uint
     int r;
     if ((r = check_subchannels(h, list, n))) return r;
     for (auto& l : h->subch_next) l.assign(list, list + n);
+    for (auto& k : h->kind_next) k.assign(n, DABPHY_AUDIO_DABPLUS);     // (a new list: every position DAB+ until kinds are set again)
+    h->kinds_dirty = true;
     h->subch_dirty = true;
     return apply_subchannels(h);
 }
@@ -461,6 +467,8 @@ int dabphy_set_subchannels_ensemble(dabphy_handle* h, uint32_t ensemble, const d
     int r;
     if ((r = check_subchannels(h, list, n))) return r;
     h->subch_next[ensemble].assign(list, list + n);
+    h->kind_next[ensemble].assign(n, DABPHY_AUDIO_DABPLUS);
+    h->kinds_dirty = true;
     h->subch_dirty = true;
     return DABPHY_OK;
 }
@@ -499,6 +507,7 @@ int apply_subchannels(dabphy_handle* h)
     const std::vector<std::vector<dabphy_subchannel>> old_lists = h->subch_e;
     h->fplan.valid = false; h->fplan.launched = false; h->buf_gen++;          // the plan names the classes' buffers
     h->last_frames = 0; h->last_desc = nullptr; h->sf_stats_ready = false; h->h_sf_stats_valid = false;   // the class outputs of the last batch go with the classes
+    h->mp2_done = false;
     h->subch_e = h->subch_next;
     h->subch_dirty = false;
     auto fail = [&](int code) {                             // nothing half-built stays: the handle then decodes no sub-channel at all
@@ -536,6 +545,7 @@ int apply_subchannels(dabphy_handle* h)
                 break;
             }
             h->where[b][i] = dabphy_handle::PairRef{ci, (int)c.pairs.size()};
+            c.kind.push_back(from.old_cls >= 0 ? old[from.old_cls].kind[from.old_pair] : DABPHY_AUDIO_DABPLUS);   // (the kind its MP2 state belongs to)
             c.pairs.push_back(p); c.subch_id.push_back(sc.subch_id); c.start_cu.push_back(sc.start_cu);
             carry[ci].push_back(from);
         }
@@ -582,6 +592,20 @@ int apply_subchannels(dabphy_handle* h)
                 if (hipMemcpyAsync(c.sf_state.as<uint8_t>() + p * stride, old[f.old_cls].sf_state.as<uint8_t>() + (size_t)f.old_pair * stride, (e - p) * stride,
                                    hipMemcpyDeviceToDevice, h->stream) != hipSuccess) { h->err = "hipMemcpyAsync(superframe windows) failed"; return fail(DABPHY_ERR_HIP); }
                 p = e;
+            }
+        }
+        // MP2 parser state of the MP2 services that stay (apply_audio_kinds, next, sets up the rest)
+        bool any_mp2 = false;
+        for (size_t p = 0; p < c.pairs.size(); p++) any_mp2 |= c.kind[p] == DABPHY_AUDIO_MP2;
+        if (any_mp2) {
+            const size_t stride = mp2_stride(), n = c.pairs.size();
+            if ((r = ensure(h, c.mp2_state, stride * n))) return fail(r);
+            if (hipMemsetAsync(c.mp2_state.p, 0, c.mp2_state.cap, h->stream) != hipSuccess) { h->err = "hipMemsetAsync(MP2 state) failed"; return fail(DABPHY_ERR_HIP); }
+            for (size_t p = 0; p < n; p++) {
+                const Carry f = carry[ci][p];
+                if (c.kind[p] != DABPHY_AUDIO_MP2 || f.old_cls < 0 || !old[f.old_cls].mp2_state.p) continue;
+                if (hipMemcpyAsync(c.mp2_state.as<uint8_t>() + p * stride, old[f.old_cls].mp2_state.as<uint8_t>() + (size_t)f.old_pair * stride, stride,
+                                   hipMemcpyDeviceToDevice, h->stream) != hipSuccess) { h->err = "hipMemcpyAsync(MP2 state) failed"; return fail(DABPHY_ERR_HIP); }
             }
         }
     }

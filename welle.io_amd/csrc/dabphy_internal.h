@@ -5,6 +5,7 @@
 //   dabphy_process.hip      dabphy_process: the pipelined schedules, exact batch mode (replay), the decode of one batch
 //   dabphy_fused.hip        the fused decode's host side: per-class step tables, the launch plan (build, classes, work list)
 //   dabphy_superframes.hip  Reed-Solomon seams and the DAB+ superframe filter
+//   dabphy_mp2.hip          classic DAB (MP2) services: audio kinds, the MP2 frame check and its unit entry
 //   dabphy_getters.hip      everything a caller reads back after a batch, profiling, TII
 #pragma once
 #define DABPHY_BUILDING_LIBRARY          // (the exported symbol `dabphy_create` is the frozen round-3 entry point here, not the header's inline)
@@ -82,6 +83,11 @@ struct dabphy_handle {
         DevBuf sf_state;                     // SuperframeFilter window of every pair
         size_t sf_pair0 = 0, sf_bytes0 = 0;  // this class's region of the filter's shared event / count / verdict buffers (in pairs) and of its superframe buffer (in bytes): prepare_superframes
         DevBuf sf_snap;                      // ... as it was in front of the current batch (exact batch mode)
+        // classic DAB (MP2) services (dabphy_mp2.hip): the audio kind of every pair as applied, device lists of the DAB+ / MP2 pairs (only
+        // when the class has an MP2 pair: otherwise the DAB+ filter walks every pair as before), the MP2 parser state and its results
+        std::vector<int32_t> kind;
+        DevBuf dab_run, mp2_run; int n_dab = 0, n_mp2 = 0;
+        DevBuf mp2_state, mp2_snap, mp2_ev, mp2_n, mp2_err, mp2_fu;
         bool dabplus_rate() const { return (prot.nbits / 24) % 8 == 0 && prot.nbits / 8 >= 10; }
         size_t sf_stride() const { return ((size_t)16 + 5 * (size_t)(prot.nbits / 8) + 15) & ~(size_t)15; }
     };
@@ -96,6 +102,11 @@ struct dabphy_handle {
     std::vector<std::vector<dabphy_subchannel>> subch_e, subch_next;     // [n_ensembles]
     std::vector<std::vector<PairRef>> where;                             // [n_ensembles][position in the list] -> class, pair
     bool subch_dirty = false;
+    std::vector<std::vector<int32_t>> kind_next;                         // [n_ensembles][position]: dabphy_set_audio_kinds_ensemble (reset by a new list)
+    bool kinds_dirty = false;
+    bool mp2_auto = false, mp2_done = false;                             // dabphy_set_auto_mp2; the MP2 pass has run for the last batch
+    hipEvent_t ev_mp2[2] = {nullptr, nullptr}; bool mp2_timed = false;   // the last MP2 pass, with profiling on (dabphy_get_mp2_ms)
+    DevBuf mp2_stats, mp2_chk_state, mp2_chk_ev, mp2_chk_n, mp2_chk_err, mp2_chk_fu;
     std::vector<MscClass> classes;
     DevBuf sf_batch; void* h_sf_batch = nullptr;                         // argument blocks of the filter's per-bucket launches (device, page-locked staging)
     DevBuf sf_run;                                                       // pair selections of one-sub-channel superframe filter launches
@@ -267,6 +278,10 @@ DABPHY_INTERNAL int resolve_chain(dabphy_handle* h, int sel);
 DABPHY_INTERNAL int prepare_superframes(dabphy_handle* h, uint32_t F);       // dabphy_superframes.hip
 DABPHY_INTERNAL int run_superframes(dabphy_handle* h, const std::vector<dabphy::SfSel>& sel, int32_t* stats, hipStream_t st = nullptr, const FrameDesc* desc = nullptr, uint32_t n_frames = 0);
 DABPHY_INTERNAL int apply_subchannels(dabphy_handle* h);                                          // dabphy_api.hip
+DABPHY_INTERNAL int apply_audio_kinds(dabphy_handle* h);                                          // dabphy_mp2.hip
+DABPHY_INTERNAL int prepare_mp2(dabphy_handle* h, uint32_t F);
+DABPHY_INTERNAL int launch_mp2_pass(dabphy_handle* h, uint32_t F);
+DABPHY_INTERNAL size_t mp2_stride();
 DABPHY_INTERNAL int upload_pairs(dabphy_handle* h, dabphy_handle::MscClass& cls);
 DABPHY_INTERNAL void free_class(dabphy_handle::MscClass& c);
 DABPHY_INTERNAL int launch_superframe_stats(dabphy_handle* h, hipStream_t st = nullptr, const FrameDesc* desc = nullptr, uint32_t n_frames = 0);

@@ -317,6 +317,30 @@ struct SfArgs {
 // the classes of one launch (k_rs.hip): cls = DEVICE array of n_cls argument blocks, first = DEVICE array [n_cls + 1] of first blocks
 struct SfBatch { const SfArgs* cls; const int32_t* first; int n_cls; };
 inline int sf_bucket(int frame_bytes) { const int sf_len = 5 * frame_bytes; return sf_len <= 960 ? 0 : sf_len <= 2880 ? 1 : 2; }
+// MP2 frame check (k_mp2.hip): MP2Decoder::Feed / CheckCRC over the logical frames of classic DAB services
+constexpr int MP2_RING = 8192;             // LDS ring of a service's byte stream
+constexpr int MP2_CARRY = 4096;            // bytes a service can carry to the next batch (what mpg123 has not consumed yet)
+struct Mp2Event {          // = dabphy_mp2_event (include/dabphy.h)
+    int32_t frame; uint32_t header; int64_t offset;
+    uint8_t crc_ok, new_format, scf_crc_len, fpad[2], pad_[3];
+};
+struct Mp2State {          // per service, followed by MP2_CARRY bytes: the stream from `origin` on that a later feed can still reach
+    int64_t origin, pos, firstpos, ks;    // absolute stream offsets: carried bytes, read position, NEED_MORE rewind point, first kept block
+    uint32_t firsthead, oldhead;
+    int32_t carry_len, header_change, framesize, fmt_rate, fmt_ch, scf_crc_len, unverified, pad_;
+};
+struct Mp2Args {
+    const uint8_t* out; int n_cif, frame_bytes;   // logical frames [pairs][n_cif][frame_bytes] (class output, or the unit entry's frames)
+    const int32_t* run;                           // the pairs to walk, one block each (nullptr: block i = pair i)
+    const MscPair* pairs;                         // nullptr: every row is a logical frame of the stream (unit entry)
+    const FrameDesc* desc; int n_frames;          // with pairs: which rows the batch decoded (as the DAB+ filter counts them)
+    uint8_t* state; size_t state_stride;          // [pairs] Mp2State + carry
+    Mp2Event* events; int ev_cap; int32_t* n_events;   // [pairs][ev_cap], [pairs] (frames the reference returned; only ev_cap stored)
+    int32_t* frame_errors;                        // [pairs][n_cif]: AudioError()s of each logical frame (what onFrameErrors reports after it)
+    int32_t* first_unverified;                    // [pairs]: logical frame from which equality is not claimed, -1
+    int32_t* stats;                               // optional [B][4]: frames checked, CRC failures, bytes skipped in resync, unverified logical frames
+};
+void launch_mp2(const Mp2Args& a, int n_blocks, hipStream_t s);
 void launch_superframe_bucket(const SfBatch& Bt, int bucket, int total_blocks, int n_cif, bool wide_pass, hipStream_t s);
 void launch_rs_superframes(const RsArgs& a, hipStream_t s);
 void launch_rs_msc(const RsMscArgs& a, hipStream_t s);

@@ -23,6 +23,7 @@ int dabphy_process(dabphy_handle* h, uint32_t n_frames)
     int r;
     if (h->subch_dirty && (h->sf_def_pending || h->sf_def_inflight) && (r = flush_deferred_superframes(h))) return r;      // (the deferred filter pass of the last batch belongs to the classes that are about to be rebuilt)
     if ((r = apply_subchannels(h))) return r;                // per-ensemble sub-channel changes since the last batch (dabphy_set_subchannels_ensemble)
+    if ((r = apply_audio_kinds(h))) return r;                // ... and audio kinds (dabphy_set_audio_kinds_ensemble)
     for (int k = 0; k < dabphy_handle::N_DESC; k++) {
         if ((r = ensure(h, h->s_desc2[k], (size_t)B * h->cfg.max_frames * sizeof(FrameDesc)))) return r;
         if ((r = ensure(h, h->s_redo[k], (size_t)B * sizeof(int32_t)))) return r;
@@ -62,6 +63,7 @@ int dabphy_process(dabphy_handle* h, uint32_t n_frames)
             if ((r = ensure(h, cls.out, n_groups * 64 * (cls.prot.nbits / 8)))) return r;
         }
         if (h->sf_auto && (r = prepare_superframes(h, F))) return r;
+        if (h->mp2_auto && (r = prepare_mp2(h, F))) return r;
         // (the replay of exact batch mode decodes one frame's FIC at a time, state-parallel when 4 B code words are few: its buffers now)
         if (replay_armed(h, F) && sp_single_ok(h, (uint64_t)B * 4, fic_c.nsteps) && (r = sp_single_reserve(h, (uint64_t)B * 4, fic_c.nsteps))) return r;
         // the fused decode of this batch depth: which classes (and whether the FIC) ride in the one launch; its decision scratch
@@ -312,6 +314,7 @@ int dabphy_process(dabphy_handle* h, uint32_t n_frames)
         launch_copy_out(h->sf_stats.p, h->h_sf_stats, sizeof(int32_t) * 4 * B, h->stream);
         h->h_sf_stats_valid = true;
     }
+    if (h->mp2_auto && (r = launch_mp2_pass(h, F))) return r;
     return DABPHY_OK;
     };
     if (replay_armed(h, F)) {
@@ -320,8 +323,10 @@ int dabphy_process(dabphy_handle* h, uint32_t n_frames)
         HIPCHK(h, hipMemcpyAsync(h->snap_dec.p, h->d_dec, sizeof(DecState) * B, hipMemcpyDeviceToDevice, h->stream));
         if (h->tii_state.p && h->snap_tii.p) HIPCHK(h, hipMemcpyAsync(h->snap_tii.p, h->tii_state.p, h->tii_state.cap, hipMemcpyDeviceToDevice, h->stream));
         if (!h->sf_deferred) for (auto& cls : h->classes) if (cls.sf_state.p && cls.sf_snap.p) HIPCHK(h, hipMemcpyAsync(cls.sf_snap.p, cls.sf_state.p, cls.sf_state.cap, hipMemcpyDeviceToDevice, h->stream));
+        if (h->mp2_auto) for (auto& cls : h->classes) if (cls.n_mp2 && cls.mp2_snap.p) HIPCHK(h, hipMemcpyAsync(cls.mp2_snap.p, cls.mp2_state.p, cls.mp2_state.cap, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemsetAsync(h->d_any_eff, 0, sizeof(int32_t), h->stream));
     }
+    h->mp2_done = false;                                     // (this batch's MP2 pass: in decode() with dabphy_set_auto_mp2, else the first getter's)
     if ((r = decode(false))) return r;
     if (depth) {
         if (h->cfg.pipeline_sync != 2) HIPCHK(h, hipStreamWaitEvent(h->sync_stream, h->ev_chain_gate, 0));
@@ -348,6 +353,7 @@ int dabphy_process(dabphy_handle* h, uint32_t n_frames)
         HIPCHK(h, hipMemcpyAsync(h->d_dec, h->snap_dec.p, sizeof(DecState) * B, hipMemcpyDeviceToDevice, h->stream));
         if (h->tii_state.p && h->snap_tii.p) HIPCHK(h, hipMemcpyAsync(h->tii_state.p, h->snap_tii.p, h->tii_state.cap, hipMemcpyDeviceToDevice, h->stream));
         if (!h->sf_deferred) for (auto& cls : h->classes) if (cls.sf_state.p && cls.sf_snap.p) HIPCHK(h, hipMemcpyAsync(cls.sf_state.p, cls.sf_snap.p, cls.sf_state.cap, hipMemcpyDeviceToDevice, h->stream));
+        if (h->mp2_auto) for (auto& cls : h->classes) if (cls.n_mp2 && cls.mp2_snap.p) HIPCHK(h, hipMemcpyAsync(cls.mp2_state.p, cls.mp2_snap.p, cls.mp2_state.cap, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemsetAsync(h->d_any_eff, 0, sizeof(int32_t), h->stream));
         if ((r = decode(true))) return r;
         HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_fic_done, 0));

@@ -138,6 +138,8 @@ int dabphy_reset(dabphy_handle* h)
     if (h->rs_stream) HIPCHK(h, hipStreamSynchronize(h->rs_stream));
     h->sf_def_pending = h->sf_def_unfetched = h->sf_def_inflight = false;      // (a deferred filter pass of the stream that ends here is dropped with it)
     for (auto& c : h->classes) if (c.sf_state.p) HIPCHK(h, hipMemsetAsync(c.sf_state.p, 0, c.sf_state.cap, h->stream));   // decoders restart too (RadioReceiver::restart_decoder)
+    for (auto& c : h->classes) if (c.mp2_state.p) HIPCHK(h, hipMemsetAsync(c.mp2_state.p, 0, c.mp2_state.cap, h->stream));   // (MP2 parsers too)
+    h->mp2_done = false;
     // ... and the frame count starts over: every selected sub-channel's time de-interleaver fills again from the first CIF decoded
     for (auto& c : h->classes) { for (MscPair& p : c.pairs) p.cif0 = -1; int r2 = upload_pairs(h, c); if (r2) return r2; }
     if (h->tii_state.p) HIPCHK(h, hipMemsetAsync(h->tii_state.p, 0, h->tii_state.cap, h->stream));      // a new OFDMProcessor owns a new TIIDecoder

@@ -212,6 +212,7 @@ int dabphy_superframes(dabphy_handle* h, uint32_t subch_index, dabphy_sf_event* 
         rows[b] = h->where[b][subch_index];
         const auto& cls = h->classes[rows[b].cls];
         if (!cls.dabplus_rate()) { h->err = "sub-channel bit rate is not a DAB+ rate"; return DABPHY_ERR_INVALID; }
+        if (cls.kind[rows[b].pair] == DABPHY_AUDIO_MP2) { h->err = "ensemble " + std::to_string(b) + ": the sub-channel is an MP2 service"; return DABPHY_ERR_INVALID; }
         if (fb && fb != cls.prot.nbits / 8) { h->err = "the ensembles' sub-channels at this position differ in bit rate: use dabphy_superframes_ensemble"; return DABPHY_ERR_INVALID; }
         fb = cls.prot.nbits / 8;
     }
@@ -225,6 +226,7 @@ int dabphy_superframes_ensemble(dabphy_handle* h, uint32_t ensemble, uint32_t su
     const std::vector<dabphy_handle::PairRef> rows(1, h->where[ensemble][subch_index]);
     const auto& cls = h->classes[rows[0].cls];
     if (!cls.dabplus_rate()) { h->err = "sub-channel bit rate is not a DAB+ rate"; return DABPHY_ERR_INVALID; }
+    if (cls.kind[rows[0].pair] == DABPHY_AUDIO_MP2) { h->err = "the sub-channel is an MP2 service (dabphy_set_audio_kinds_ensemble)"; return DABPHY_ERR_INVALID; }
     return superframes_of(h, rows, cls.prot.nbits / 8, events, n_events, sf);
 }
 
@@ -237,7 +239,12 @@ int launch_superframe_stats(dabphy_handle* h, hipStream_t st, const FrameDesc* d
     if ((r = ensure(h, h->sf_stats, sizeof(int32_t) * 4 * B))) return r;
     HIPCHK(h, hipMemsetAsync(h->sf_stats.p, 0, sizeof(int32_t) * 4 * B, st));
     std::vector<SfSel> sel;
-    for (size_t ci = 0; ci < h->classes.size(); ci++) if (h->classes[ci].dabplus_rate()) sel.push_back(SfSel{(int)ci, nullptr, 0});
+    for (size_t ci = 0; ci < h->classes.size(); ci++) {
+        const auto& c = h->classes[ci];
+        if (!c.dabplus_rate()) continue;
+        if (!c.n_mp2) sel.push_back(SfSel{(int)ci, nullptr, 0});
+        else if (c.n_dab) sel.push_back(SfSel{(int)ci, c.dab_run.as<int32_t>(), c.n_dab});      // (MP2 services are left out: dabphy_mp2.hip)
+    }
     if (sel.empty()) return 0;
     if (h->profiling) { hipError_t e = hipEventRecord(h->ev_beg[dabphy_handle::ST_RS], st); (void)e; }
     if ((r = run_superframes(h, sel, h->sf_stats.as<int32_t>(), st, desc, n_frames))) return r;

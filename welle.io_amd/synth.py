@@ -532,3 +532,124 @@ def dabplus_payload_fn(period_cifs=80, seed=0):
         fb = s.frame_bytes
         return cache[key][(r % 5) * fb:(r % 5 + 1) * fb].tobytes()
     return fn
+
+
+# --- MPEG-1/2 Layer II ("MP2") audio frames of classic DAB services (ETSI TS 103 466) -------------------------------------
+# bit allocation widths as MP2Decoder::CheckCRC chooses them (dab_decoder.cpp:21-50): ISO/IEC 11172-3 tables B.2a / B.2c and
+# ISO/IEC 13818-3 table B.1
+MP2_NBAL = ((4,) * 11 + (3,) * 12 + (2,) * 4, (4, 4) + (3,) * 6, (4,) * 4 + (3,) * 7 + (2,) * 19)
+MP2_BITRATES = ((0, 32, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320, 384),      # MPEG-1 Layer II (48 kHz)
+                (0, 8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128, 144, 160))           # MPEG-2 LSF Layer II (24 kHz)
+MP2_MODES = {"stereo": 0, "joint": 1, "dual": 2, "mono": 3}
+
+
+def mp2_table_index(lsf, bitrate, nch):
+    return 2 if lsf else (0 if bitrate // nch >= 56 else 1)
+
+
+def make_mp2_frame(bitrate, rng, rate=48000, mode="stereo", mode_ext=0, fpad=None):
+    """one Layer II frame of 144000 * bitrate / rate bytes (3 or 6 x bitrate: one or two logical frames) with CRC: random bit
+    allocation (kept within the frame's bit budget), ScFSI, scale factors and samples (random bytes), ScF-CRC and F-PAD at the end"""
+    lsf = rate == 24000
+    mode_v = MP2_MODES[mode]
+    nch = 1 if mode_v == 3 else 2
+    bri = MP2_BITRATES[1 if lsf else 0].index(bitrate)
+    size = 144000 * bitrate // rate
+    ti = mp2_table_index(lsf, bitrate, nch)
+    nbal = MP2_NBAL[ti]
+    sblimit = len(nbal)
+    bound = min((mode_ext + 1) * 4, sblimit) if mode_v == 1 else sblimit
+    scf_crc_len = 2 if (not lsf and bitrate < (56 if nch == 1 else 112)) else 4
+    budget = (size - 4 - 2 - scf_crc_len - 2) * 8 - sum(nbal[sb] * (nch if sb < bound else 1) for sb in range(sblimit))
+    alloc = [[0] * nch for _ in range(sblimit)]
+    for sb in range(sblimit):
+        for ch in (range(nch) if sb < bound else range(1)):
+            if rng.randint(0, 3) == 0:
+                v = int(rng.randint(1, 1 << nbal[sb]))
+                cost = (2 + 18 + 36 * 16) * (1 if sb < bound else nch)     # ScFSI + three scale factors + 36 samples of <= 16 bits
+                if cost <= budget:
+                    budget -= cost
+                    alloc[sb][ch] = v
+    head = 0xFFF00000 | ((0 if lsf else 1) << 19) | (2 << 17) | (0 << 16) | (bri << 12) | (1 << 10) | (mode_v << 6) | (mode_ext << 4) | 4
+    bits = []
+
+    def put(v, n):
+        bits.extend((v >> (n - 1 - i)) & 1 for i in range(n))
+    for sb in range(sblimit):
+        for ch in (range(nch) if sb < bound else range(1)):
+            put(alloc[sb][ch], nbal[sb])
+    for sb in range(sblimit):
+        for ch in range(nch):
+            if alloc[sb][ch if sb < bound else 0]:
+                put(int(rng.randint(0, 4)), 2)
+    ncrc = len(bits)
+    frame = np.zeros(size, np.uint8)
+    frame[:4] = [(head >> 24) & 0xFF, (head >> 16) & 0xFF, (head >> 8) & 0xFF, head & 0xFF]
+    frame[6:] = rng.randint(0, 256, size - 6)
+    pb = np.packbits(np.array(bits + [0] * (-len(bits) % 8), np.uint8))
+    # the covered bits replace the random ones; the bits after them in the last byte stay random
+    nfull = ncrc // 8
+    frame[6:6 + nfull] = pb[:nfull]
+    if ncrc % 8:
+        keep = 0xFF >> (ncrc % 8)
+        frame[6 + nfull] = (int(pb[nfull]) & ~keep & 0xFF) | (int(frame[6 + nfull]) & keep)
+    if fpad is not None:
+        frame[-2:] = fpad
+    frame[4:6] = np.frombuffer(mp2_crc(frame).to_bytes(2, "big"), np.uint8)
+    return frame.tobytes()
+
+
+def mp2_crc(frame):
+    """the CRC MP2Decoder::CheckCRC expects in bytes 4..5 of a frame (tools.cpp:36: CRC-16, polynomial 0x8005, inverted initial
+    value): header bytes 2 and 3, then the allocation and ScFSI bits"""
+    frame = np.frombuffer(bytes(frame), np.uint8)
+    h = int.from_bytes(frame[:4].tobytes(), "big")
+    lsf = not (h >> 19) & 1
+    bitrate = MP2_BITRATES[1 if lsf else 0][(h >> 12) & 15]
+    mode, mode_ext = (h >> 6) & 3, (h >> 4) & 3
+    nch = 1 if mode == 3 else 2
+    nbal = MP2_NBAL[mp2_table_index(lsf, bitrate, nch)]
+    sblimit = len(nbal)
+    bound = min((mode_ext + 1) * 4, sblimit) if mode == 1 else sblimit
+    bits = np.unpackbits(frame[6:])
+    p = 0
+    n = 0
+    for sb in range(sblimit):
+        for ch in (range(nch) if sb < bound else range(1)):
+            v = int("".join(map(str, bits[p:p + nbal[sb]])) or "0", 2)
+            p += nbal[sb]
+            n += nbal[sb] + (2 if v and sb < bound else 0) + (2 * nch if v and sb >= bound else 0)
+    crc = 0xFFFF
+    for byte in frame[2:4]:
+        for i in range(8):
+            crc = _crc_bit(crc, (int(byte) >> (7 - i)) & 1)
+    for i in range(n):
+        crc = _crc_bit(crc, int(bits[i]))
+    return crc
+
+
+def _crc_bit(crc, bit):
+    fb = ((crc >> 15) & 1) ^ bit
+    crc = (crc << 1) & 0xFFFF
+    return crc ^ 0x8005 if fb else crc
+
+
+def mp2_payload_fn(period_cifs=64, seed=0, rate=48000, mode="stereo", mode_ext=0):
+    """payload_fn for EnsembleTx: Layer II frames with CRC (make_mp2_frame), periodic with period_cifs (a multiple of 16, so a
+    recording of period_cifs/4 transmission frames loops without breaking the time interleaver; even, so LSF frames of two
+    logical frames each loop too)"""
+    assert period_cifs % 16 == 0
+    per = 2 if rate == 24000 else 1
+    cache = {}
+
+    def fn(s, r):
+        r = r % period_cifs
+        q = r // per
+        key = (s.subch_id, q)
+        if key not in cache:
+            # (a frame of 144000 * bitrate / rate bytes is per logical frames of 3 x bitrate bytes: the sub-channel's bit rate)
+            cache[key] = make_mp2_frame(s.bitrate, np.random.RandomState(seed * 1000003 + s.subch_id * 1009 + q), rate=rate, mode=mode,
+                                        mode_ext=mode_ext)
+        fb = s.frame_bytes
+        return cache[key][(r % per) * fb:(r % per + 1) * fb]
+    return fn

@@ -121,6 +121,24 @@ def make_base_streams(n_distinct, n_frames=REC_FRAMES, seed0=0, subchs=None):
     return np.stack(out), txs
 
 
+def make_mp2_base_streams(n_distinct, n_frames=REC_FRAMES, seed0=0, every=4):
+    """make_base_streams' canonical multiplex (18 x 64 kbit/s) with every `every`-th sub-channel carrying Layer II frames (48 kHz stereo,
+    synth.mp2_payload_fn) instead of DAB+ superframes -> (recordings [n_distinct][N], sub-channels, list positions of the MP2 services)"""
+    subchs = synth.default_subchannels()
+    mp2_pos = [i for i in range(len(subchs)) if i % every == 0]
+    ids = {subchs[i].subch_id for i in mp2_pos}
+    out = []
+    for e in range(n_distinct):
+        dab = synth.dabplus_payload_fn(4 * n_frames, seed0 + e)
+        mp2 = synth.mp2_payload_fn(4 * n_frames, seed0 + e)
+        tx = synth.EnsembleTx(eid=0x1000 + seed0 + e, subchs=subchs, seed=seed0 + e,
+                              payload_fn=lambda s, r, dab=dab, mp2=mp2: (mp2 if s.subch_id in ids else dab)(s, r))
+        for _ in range(n_frames):
+            tx.next_frame()
+        out.append(np.concatenate([tx.next_frame() for _ in range(n_frames)]).astype(np.complex64))
+    return np.stack(out), subchs, mp2_pos
+
+
 def make_batch(B, rank=0, n_distinct=4, cfo_max_hz=60.0, sigma=0.02, device="cuda", base=None, rec_frames=REC_FRAMES):
     """-> (iq [B][N] complex64 torch tensor on `device`, per-ensemble carrier offsets in Hz, base recordings, their transmitters)"""
     import torch
