@@ -2,6 +2,8 @@
 #include "hip/hip_runtime.h"
 #include <stdexcept>
 #include <mutex>
+#include <set>
+#include <utility>
 
 hipemu_idx threadIdx, blockIdx, blockDim, gridDim;
 
@@ -123,4 +125,64 @@ void hipemu_launch(dim3 grid, dim3 block, const std::function<void()>& body) {
         }
     }
     g_body = nullptr;
+}
+
+// ---- what is alive: device blocks, page-locked blocks, streams, events.  A stream is a distinct non-null object (two fields of a handle
+// that name the same stream compare equal, two streams never do); releasing what is not alive -- a second time, or something never
+// created -- aborts with a message.
+namespace {
+enum { LIVE_DEV = 0, LIVE_HOST, LIVE_STREAM, LIVE_EVENT, LIVE_KINDS };
+const char* const live_name[LIVE_KINDS] = {"hipFree", "hipHostFree", "hipStreamDestroy", "hipEventDestroy"};
+std::mutex g_live_mutex;
+std::set<const void*> g_live[LIVE_KINDS];
+std::vector<std::pair<int64_t, int64_t>> g_stream_log;
+struct StreamObj { unsigned flags; int priority; };
+
+void born(int kind, const void* p) { std::lock_guard<std::mutex> l(g_live_mutex); g_live[kind].insert(p); }
+void gone(int kind, const void* p)
+{
+    std::lock_guard<std::mutex> l(g_live_mutex);
+    if (g_live[kind].erase(p) == 1) return;
+    fprintf(stderr, "hipemu: %s(%p): not alive (released twice, or never created)\n", live_name[kind], p);
+    abort();
+}
+hipError_t new_block(int kind, void** p, size_t n)
+{
+    *p = aligned_alloc(256, (n + 255) / 256 * 256 + 256);
+    if (!*p) return 2;
+    born(kind, *p);
+    return hipSuccess;
+}
+hipError_t new_stream(hipStream_t* s, unsigned flags, int priority)
+{
+    *s = new StreamObj{flags, priority};
+    born(LIVE_STREAM, *s);
+    std::lock_guard<std::mutex> l(g_live_mutex);
+    g_stream_log.emplace_back((int64_t)flags, (int64_t)priority);
+    return hipSuccess;
+}
+}
+
+hipError_t hipMalloc(void** p, size_t n) { return new_block(LIVE_DEV, p, n); }
+hipError_t hipFree(void* p) { if (p) { gone(LIVE_DEV, p); free(p); } return hipSuccess; }
+hipError_t hipHostMalloc(void** p, size_t n, unsigned) { return new_block(LIVE_HOST, p, n); }
+hipError_t hipHostFree(void* p) { if (p) { gone(LIVE_HOST, p); free(p); } return hipSuccess; }
+hipError_t hipStreamCreate(hipStream_t* s) { return new_stream(s, 0, 0); }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned flags) { return new_stream(s, flags, 0); }
+hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned flags, int priority) { return new_stream(s, flags, priority); }
+hipError_t hipStreamDestroy(hipStream_t s) { gone(LIVE_STREAM, s); delete static_cast<StreamObj*>(s); return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t* e) { *e = new hipemu_event; born(LIVE_EVENT, *e); return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
+hipError_t hipEventDestroy(hipEvent_t e) { gone(LIVE_EVENT, e); delete e; return hipSuccess; }
+
+extern "C" void hipemu_live_counts(int64_t out[4])
+{
+    std::lock_guard<std::mutex> l(g_live_mutex);
+    for (int k = 0; k < LIVE_KINDS; k++) out[k] = (int64_t)g_live[k].size();
+}
+extern "C" int64_t hipemu_stream_creations(int64_t* flags_priority, int64_t cap)
+{
+    std::lock_guard<std::mutex> l(g_live_mutex);
+    for (int64_t i = 0; i < cap && i < (int64_t)g_stream_log.size(); i++) { flags_priority[2 * i] = g_stream_log[i].first; flags_priority[2 * i + 1] = g_stream_log[i].second; }
+    return (int64_t)g_stream_log.size();
 }

@@ -81,20 +81,9 @@ int dabphy_create_v2(const dabphy_config* cfg_in, dabphy_handle** out)
     if ((r = upload_const(h, &h->d_osc_unsafe, T.osc_unsafe))) return fail(r);
     h->tab.tw = h->d_tw; h->tab.ref = h->d_ref; h->tab.nco = h->d_nco; h->tab.bin2soft = h->d_bin2soft; h->tab.prbs_bytes = nullptr;
     h->tab.osc_unsafe = h->d_osc_unsafe; h->tab.n_osc_unsafe = T.n_osc_unsafe;
-    {
-        void* p = nullptr;
-        if (hipMalloc(&p, 2 * sizeof(unsigned long long)) != hipSuccess) return fail(DABPHY_ERR_NOMEM);
-        h->owned.push_back(p); h->d_osc_stats = reinterpret_cast<unsigned long long*>(p);
-        if (hipMemset(p, 0, 2 * sizeof(unsigned long long)) != hipSuccess) return fail(DABPHY_ERR_HIP);
-    }
-    void* st = nullptr;
-    if (hipMalloc(&st, sizeof(RxState) * cfg->n_ensembles) != hipSuccess) return fail(DABPHY_ERR_NOMEM);
-    h->owned.push_back(st); h->d_state = reinterpret_cast<RxState*>(st);
-    if (hipMemset(st, 0, sizeof(RxState) * cfg->n_ensembles) != hipSuccess) return fail(DABPHY_ERR_HIP);
-    void* ds = nullptr;
-    if (hipMalloc(&ds, sizeof(DecState) * cfg->n_ensembles) != hipSuccess) return fail(DABPHY_ERR_NOMEM);
-    h->owned.push_back(ds); h->d_dec = reinterpret_cast<DecState*>(ds);
-    if (hipMemset(ds, 0, sizeof(DecState) * cfg->n_ensembles) != hipSuccess) return fail(DABPHY_ERR_HIP);
+    if ((r = device_block(h, &h->d_osc_stats, 2, true))) return fail(r);
+    if ((r = device_block(h, &h->d_state, cfg->n_ensembles, true))) return fail(r);
+    if ((r = device_block(h, &h->d_dec, cfg->n_ensembles, true))) return fail(r);
     {
         // Stream placement.  Measured in round 6 (tools/probe_handle_order.py, profiles/r06_step_variants.txt): the SECOND handle a process
         // opens decodes the benchmark batch 3 % faster than the first (decoder 6.0 against 6.6-6.7 ms, step 10.1 against 10.4) -- also
@@ -103,73 +92,49 @@ int dabphy_create_v2(const dabphy_config* cfg_in, dabphy_handle** out)
         // order), i.e. who wins the wave slots when the decoder and the next batch's synchroniser become ready together.  A handle
         // therefore first creates the five streams such a predecessor would have created -- same order, same priorities, never used --
         // and keeps them until it is destroyed.
-        int lo = 0, hi = 0;
-        if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { lo = 0; hi = 0; }
         int n_placeholders = 5;
 #ifdef DABPHY_EXPERIMENTS
         if (const char* e = getenv("DABPHY_STREAM_LAYOUT")) { h->stream_layout = atoi(e); n_placeholders = (h->stream_layout & 1) ? 5 : 0; }      // (tools/probe_streams.py)
 #endif
-        for (int i = 0; i < n_placeholders; i++) {
-            hipStream_t ps = nullptr;
-            if ((i == 1 ? hipStreamCreateWithPriority(&ps, hipStreamNonBlocking, hi) : hipStreamCreateWithFlags(&ps, hipStreamNonBlocking)) != hipSuccess) return fail(DABPHY_ERR_HIP);
-            h->placeholder_streams.push_back(ps);
-        }
+        hipStream_t placeholder = nullptr;
+        for (int i = 0; i < n_placeholders; i++) if ((r = new_stream(h, &placeholder, i == 1))) return fail(r);
     }
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(DABPHY_ERR_HIP);
-    {   // the frame chain is short serial work: give its queue the highest dispatch priority
-        int lo = 0, hi = 0;
-        if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { lo = 0; hi = 0; }
-        if (hipStreamCreateWithPriority(&h->sync_stream, hipStreamNonBlocking, hi) != hipSuccess) return fail(DABPHY_ERR_HIP);
-    }
-    if (hipEventCreate(&h->ev_sync_done) != hipSuccess) return fail(DABPHY_ERR_HIP);
-    if (hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking) != hipSuccess) return fail(DABPHY_ERR_HIP);
-    if (hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) != hipSuccess) return fail(DABPHY_ERR_HIP);
+    if ((r = new_stream(h, &h->stream))) return fail(r);
+    if ((r = new_stream(h, &h->sync_stream, true))) return fail(r);      // the frame chain is short serial work: give its queue the highest dispatch priority
+    if ((r = new_stream(h, &h->aux_stream))) return fail(r);
+    if ((r = new_stream(h, &h->copy_stream))) return fail(r);
     if (h->stream_layout & 2) h->fic_stream = h->aux_stream;      // (experiment: fewer streams -- measured slower, profiles/r06_step_variants.txt)
-    else if (hipStreamCreateWithFlags(&h->fic_stream, hipStreamNonBlocking) != hipSuccess) return fail(DABPHY_ERR_HIP);
-    if (hipEventCreateWithFlags(&h->ev_aux_done, hipEventDisableTiming) != hipSuccess) return fail(DABPHY_ERR_HIP);
-    for (int i = 0; i < 2; i++) if (hipEventCreateWithFlags(&h->ev_ingest[i], hipEventDisableTiming) != hipSuccess) return fail(DABPHY_ERR_HIP);
-    if (hipEventCreateWithFlags(&h->ev_chain_gate, hipEventDisableTiming) != hipSuccess) return fail(DABPHY_ERR_HIP);
-    if (hipEventCreateWithFlags(&h->ev_demod_done, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h->ev_fic_done, hipEventDisableTiming) != hipSuccess) return fail(DABPHY_ERR_HIP);
-    if (hipEventCreateWithFlags(&h->ev_fused_done, hipEventDisableTiming) != hipSuccess) return fail(DABPHY_ERR_HIP);
+    else if ((r = new_stream(h, &h->fic_stream))) return fail(r);
+    for (hipEvent_t* e : {&h->ev_aux_done, &h->ev_ingest[0], &h->ev_ingest[1], &h->ev_chain_gate, &h->ev_demod_done, &h->ev_fic_done, &h->ev_fused_done})
+        if ((r = new_event(h, e))) return fail(r);
     if ((r = fused_class_tables(h, pf, true, h->fic_steps, h->fic_windows))) return fail(r);
-    for (int i = 0; i < dabphy_handle::N_DESC; i++) if (hipEventCreate(&h->ev_chain_beg[i]) != hipSuccess || hipEventCreate(&h->ev_chain_end[i]) != hipSuccess) return fail(DABPHY_ERR_HIP);
-    for (int i = 0; i < dabphy_handle::N_DESC; i++) if (hipEventCreateWithFlags(&h->ev_wide_done[i], hipEventDisableTiming) != hipSuccess) return fail(DABPHY_ERR_HIP);
+    for (int i = 0; i < dabphy_handle::N_DESC; i++) if ((r = new_event(h, &h->ev_chain_beg[i], true)) || (r = new_event(h, &h->ev_chain_end[i], true))) return fail(r);
+    for (int i = 0; i < dabphy_handle::N_DESC; i++) if ((r = new_event(h, &h->ev_wide_done[i]))) return fail(r);
     {
         // the wide synchroniser pass's verdict flags: page-locked HOST memory the last judge kernel writes directly (d_any_redo = the
         // device's address of the same words)
-        void* p = nullptr; void* dp = nullptr;
+        void* dp = nullptr;
         // ([N_DESC] "the serial chain has slots left" + [N_DESC] "the find chain settled frames": ensembles whose window moves)
-        if (hipHostMalloc(&p, sizeof(int32_t) * 2 * dabphy_handle::N_DESC, hipHostMallocDefault) != hipSuccess) return fail(DABPHY_ERR_NOMEM);
-        h->h_any_redo = reinterpret_cast<int32_t*>(p);
+        if ((r = pinned_alloc(h, sizeof(int32_t) * 2 * dabphy_handle::N_DESC, &h->h_any_redo))) return fail(r);
         for (int i = 0; i < 2 * dabphy_handle::N_DESC; i++) h->h_any_redo[i] = 0;
-        if (hipHostGetDevicePointer(&dp, p, 0) != hipSuccess) return fail(DABPHY_ERR_HIP);
+        if (hipHostGetDevicePointer(&dp, h->h_any_redo, 0) != hipSuccess) return fail(DABPHY_ERR_HIP);
         h->d_any_redo = reinterpret_cast<int32_t*>(dp);
     }
     {
-        void* p = nullptr; const size_t n = (size_t)cfg->n_ensembles * cfg->max_frames;
-        if (hipHostMalloc(&p, n * sizeof(FrameDesc), hipHostMallocDefault) != hipSuccess) return fail(DABPHY_ERR_NOMEM);
-        h->h_desc = reinterpret_cast<FrameDesc*>(p);
-        if (hipHostMalloc(&p, n * sizeof(float), hipHostMallocDefault) != hipSuccess) return fail(DABPHY_ERR_NOMEM);
-        h->h_snr = reinterpret_cast<float*>(p);
-        if (hipHostMalloc(&p, n * 384, hipHostMallocDefault) != hipSuccess) return fail(DABPHY_ERR_NOMEM);
-        h->h_fib = reinterpret_cast<uint8_t*>(p);
-        if (hipHostMalloc(&p, n * 12, hipHostMallocDefault) != hipSuccess) return fail(DABPHY_ERR_NOMEM);
-        h->h_ok = reinterpret_cast<uint8_t*>(p);
-        if (hipHostMalloc(&p, (size_t)cfg->n_ensembles * 4 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) return fail(DABPHY_ERR_NOMEM);
-        h->h_sf_stats = reinterpret_cast<int32_t*>(p);
+        const size_t n = (size_t)cfg->n_ensembles * cfg->max_frames;
+        if ((r = pinned_alloc(h, n * sizeof(FrameDesc), &h->h_desc))) return fail(r);
+        if ((r = pinned_alloc(h, n * sizeof(float), &h->h_snr))) return fail(r);
+        if ((r = pinned_alloc(h, n * 384, &h->h_fib))) return fail(r);
+        if ((r = pinned_alloc(h, n * 12, &h->h_ok))) return fail(r);
+        if ((r = pinned_alloc(h, (size_t)cfg->n_ensembles * 4 * sizeof(int32_t), &h->h_sf_stats))) return fail(r);
     }
     h->exact_batch = cfg->no_batch_replay == 0;
 #ifdef DABPHY_EXPERIMENTS
     if (const char* e = getenv("DABPHY_EXACT_BATCH")) h->exact_batch = atoi(e) != 0;   // (experiments: overrides the configuration)
 #endif
-    {
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(int32_t)) != hipSuccess) return fail(DABPHY_ERR_NOMEM);
-        h->owned.push_back(p); h->d_any_eff = reinterpret_cast<int32_t*>(p);
-        if (hipMemset(p, 0, sizeof(int32_t)) != hipSuccess) return fail(DABPHY_ERR_HIP);
-        if (hipHostMalloc(&p, sizeof(int32_t), hipHostMallocDefault) != hipSuccess) return fail(DABPHY_ERR_NOMEM);
-        h->h_any_eff = reinterpret_cast<int32_t*>(p); *h->h_any_eff = 0;
-    }
+    if ((r = device_block(h, &h->d_any_eff, 1, true))) return fail(r);
+    if ((r = pinned_alloc(h, sizeof(int32_t), &h->h_any_eff))) return fail(r);
+    *h->h_any_eff = 0;
     h->wide_sync = cfg->serial_sync == 0;
 #ifdef DABPHY_EXPERIMENTS
     if (const char* e = getenv("DABPHY_SYNC_WIDE")) h->wide_sync = atoi(e) != 0;    // (experiments: overrides the configuration)
@@ -184,8 +149,7 @@ int dabphy_create_v2(const dabphy_config* cfg_in, dabphy_handle** out)
     if (const char* e = getenv("DABPHY_CHAIN_EARLY")) h->chain_early = atoi(e) != 0;
     if (const char* e = getenv("DABPHY_TB_SPLIT")) h->tb_split = atoi(e) != 0;      // (the fused decode's traceback as a pass of its own: dabphy_test_traceback_split)
 #endif
-    for (int i = 0; i < dabphy_handle::ST_COUNT; i++)
-        if (hipEventCreate(&h->ev_beg[i]) != hipSuccess || hipEventCreate(&h->ev_end[i]) != hipSuccess) return fail(DABPHY_ERR_HIP);
+    for (int i = 0; i < dabphy_handle::ST_COUNT; i++) if ((r = new_event(h, &h->ev_beg[i], true)) || (r = new_event(h, &h->ev_end[i], true))) return fail(r);
 #ifdef DABPHY_WRONG_RESULTS_BUILD
     fprintf(stderr, "dabphy: THIS LIBRARY WAS BUILT WITH AN FM_EXP_* TIMING SWITCH: its decoder output is wrong by construction\n");
     strncat(h->devname, " [timing-experiment build: wrong results]", sizeof h->devname - strlen(h->devname) - 1);
@@ -194,74 +158,20 @@ int dabphy_create_v2(const dabphy_config* cfg_in, dabphy_handle** out)
     return DABPHY_OK;
 }
 
-// every device buffer of one protection class (apply_subchannels replaces the classes, dabphy_destroy ends them)
-void free_class(dabphy_handle::MscClass& c)
-{
-    hipError_t e = hipSuccess;
-    DevBuf* bufs[] = {&c.map, &c.pair_tab, &c.tiles, &c.out, &c.steps[0], &c.steps[1], &c.steps[2], &c.sf_state, &c.sf_snap,
-                      &c.dab_run, &c.mp2_run, &c.mp2_state, &c.mp2_snap, &c.mp2_ev, &c.mp2_n, &c.mp2_err, &c.mp2_fu};
-    for (DevBuf* b : bufs) if (b->p) { e = hipFree(b->p); b->p = nullptr; b->cap = 0; }
-    (void)e;
-}
-
+// Everything the handle created through new_stream / new_event / pinned_alloc, then the handle: its device buffers and classes release
+// themselves in its destructor (still with the handle's device current).
 void dabphy_destroy(dabphy_handle* h)
 {
     DeviceBind dev_(h);
     if (!h) return;
-    hipError_t e;
-    if (h->sync_stream) { e = hipStreamSynchronize(h->sync_stream); e = hipStreamDestroy(h->sync_stream); }
+    hipError_t e = hipSuccess;
+    for (hipStream_t s : h->streams) e = hipStreamSynchronize(s);
 #ifdef SYNC_CHAIN_TS
     if (getenv("DABPHY_CHAIN_TS")) dump_chain_ts();
 #endif
-    if (h->ev_sync_done) e = hipEventDestroy(h->ev_sync_done);
-    if (h->aux_stream) { e = hipStreamSynchronize(h->aux_stream); e = hipStreamDestroy(h->aux_stream); }
-    if (h->copy_stream) { e = hipStreamSynchronize(h->copy_stream); e = hipStreamDestroy(h->copy_stream); }
-    if (h->fic_stream && h->fic_stream != h->aux_stream) { e = hipStreamSynchronize(h->fic_stream); e = hipStreamDestroy(h->fic_stream); }
-    for (hipStream_t ps : h->placeholder_streams) if (ps) e = hipStreamDestroy(ps);
-    if (h->drain_stream && h->drain_stream != h->copy_stream) { e = hipStreamSynchronize(h->drain_stream); e = hipStreamDestroy(h->drain_stream); }
-    if (h->tb_stream) { e = hipStreamSynchronize(h->tb_stream); e = hipStreamDestroy(h->tb_stream); }
-    if (h->ev_rs_done) e = hipEventDestroy(h->ev_rs_done);
-    if (h->ev_wide_front) e = hipEventDestroy(h->ev_wide_front);
-    if (h->h_tb_gave_up) e = hipHostFree(h->h_tb_gave_up);
-    if (h->ev_tb_fork) e = hipEventDestroy(h->ev_tb_fork);
-    if (h->ev_tb_join) e = hipEventDestroy(h->ev_tb_join);
-    if (h->ev_drain_done) e = hipEventDestroy(h->ev_drain_done);
-    if (h->ev_drain_staged) e = hipEventDestroy(h->ev_drain_staged);
-    if (h->drain_stage.p) e = hipFree(h->drain_stage.p);
-    if (h->ev_aux_done) e = hipEventDestroy(h->ev_aux_done);
-    for (int i = 0; i < 2; i++) if (h->ev_ingest[i]) e = hipEventDestroy(h->ev_ingest[i]);
-    if (h->ev_demod_done) e = hipEventDestroy(h->ev_demod_done);
-    if (h->ev_chain_gate) e = hipEventDestroy(h->ev_chain_gate);
-    for (int i = 0; i < dabphy_handle::N_DESC; i++) { if (h->ev_wide_done[i]) e = hipEventDestroy(h->ev_wide_done[i]); if (h->s_redo[i].p) e = hipFree(h->s_redo[i].p); }
-    if (h->h_any_redo) e = hipHostFree(h->h_any_redo);
-    if (h->h_desc) e = hipHostFree(h->h_desc);
-    if (h->h_snr) e = hipHostFree(h->h_snr);
-    if (h->h_fib) e = hipHostFree(h->h_fib);
-    if (h->h_ok) e = hipHostFree(h->h_ok);
-    if (h->h_sf_stats) e = hipHostFree(h->h_sf_stats);
-    if (h->h_any_eff) e = hipHostFree(h->h_any_eff);
-    for (int i = 0; i < dabphy_handle::N_DESC; i++) if (h->snap_state[i].p) e = hipFree(h->snap_state[i].p);
-    for (int i = 0; i < dabphy_handle::N_DESC; i++) if (h->snap_hist[i].p) e = hipFree(h->snap_hist[i].p);
-    if (h->snap_dec.p) e = hipFree(h->snap_dec.p);
-    if (h->snap_tii.p) e = hipFree(h->snap_tii.p);
-    if (h->ev_fic_done) e = hipEventDestroy(h->ev_fic_done);
-    if (h->ev_fused_done) e = hipEventDestroy(h->ev_fused_done);
-    { DevBuf* fb[] = {&h->fused_cls, &h->fused_work, &h->fused_dec_off, &h->fused_done, &h->fic_steps[0], &h->fic_steps[1], &h->fic_steps[2], &h->sp1_cls, &h->sp1_work}; for (DevBuf* b : fb) if (b->p) e = hipFree(b->p); }
-    if (h->h_sp1) e = hipHostFree(h->h_sp1);
-    if (h->h_sf_batch) e = hipHostFree(h->h_sf_batch);
-    for (int i = 0; i < dabphy_handle::N_DESC; i++) { if (h->ev_chain_beg[i]) e = hipEventDestroy(h->ev_chain_beg[i]); if (h->ev_chain_end[i]) e = hipEventDestroy(h->ev_chain_end[i]); }
-    if (h->stream) { e = hipStreamSynchronize(h->stream); e = hipStreamDestroy(h->stream); }
-    for (void* p : h->owned) e = hipFree(p);
-    for (int i = 0; i < dabphy_handle::ST_COUNT; i++) { if (h->ev_beg[i]) e = hipEventDestroy(h->ev_beg[i]); if (h->ev_end[i]) e = hipEventDestroy(h->ev_end[i]); }
-    DevBuf* more[] = {&h->s_raw, &h->s_raw2[0], &h->s_raw2[1], &h->s_null, &h->s_iq_own, &h->s_desc2[0], &h->s_desc2[1], &h->s_desc2[2], &h->s_soft, &h->s_cir2[0], &h->s_cir2[1], &h->s_cir2[2], &h->s_con, &h->s_mag, &h->s_snr, &h->s_fib, &h->s_ok, &h->rs_first, &h->rs_result};
-    for (DevBuf* b : more) if (b->p) e = hipFree(b->p);
-    { DevBuf* sfb[] = {&h->sf_events, &h->sf_count, &h->sf_bytes, &h->sf_stats, &h->sf_gf, &h->sf_accept, &h->sf_run, &h->sf_batch}; for (DevBuf* b : sfb) if (b->p) e = hipFree(b->p); }
-    { DevBuf* mb[] = {&h->mp2_stats, &h->mp2_chk_state, &h->mp2_chk_ev, &h->mp2_chk_n, &h->mp2_chk_err, &h->mp2_chk_fu}; for (DevBuf* b : mb) if (b->p) e = hipFree(b->p); }
-    for (int i = 0; i < 2; i++) if (h->ev_mp2[i]) e = hipEventDestroy(h->ev_mp2[i]);
-    { DevBuf* tb[] = {&h->s_hist, &h->tii_rot, &h->tii_rank, &h->tii_pat, &h->tii_err, &h->tii_likely, &h->tii_state, &h->tii_events, &h->tii_nev, &h->tii_ovf}; for (DevBuf* b : tb) if (b->p) e = hipFree(b->p); }
-    for (auto& c : h->classes) free_class(c);
-    DevBuf* bufs[] = {&h->iq, &h->soft, &h->con, &h->prs_mag, &h->snr, &h->desc, &h->in8, &h->map, &h->vsym, &h->vdec, &h->vout, &h->ok, &h->fsym, &h->fdec};
-    for (DevBuf* b : bufs) if (b->p) e = hipFree(b->p);
+    for (hipEvent_t ev : h->events) e = hipEventDestroy(ev);
+    for (hipStream_t s : h->streams) e = hipStreamDestroy(s);
+    for (void* p : h->pinned) e = hipHostFree(p);
     (void)e;
     delete h;
 }
@@ -511,9 +421,7 @@ int apply_subchannels(dabphy_handle* h)
     h->subch_e = h->subch_next;
     h->subch_dirty = false;
     auto fail = [&](int code) {                             // nothing half-built stays: the handle then decodes no sub-channel at all
-        for (auto& c : old) free_class(c);
-        for (auto& c : h->classes) free_class(c);
-        h->classes.clear();
+        h->classes.clear();                                 // (and `old` goes with the function: the classes free their buffers)
         // (the rejected request goes too: dabphy_get_subchannel_count then reports what is in effect -- nothing -- instead of sub-channels
         // that are never decoded, and the next dabphy_process has nothing stale to apply)
         for (uint32_t b = 0; b < B; b++) { h->subch_e[b].clear(); h->where[b].clear(); h->subch_next[b].clear(); }
@@ -610,22 +518,21 @@ int apply_subchannels(dabphy_handle* h)
         }
     }
     if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "hipStreamSynchronize failed (sub-channel change)"; return fail(DABPHY_ERR_HIP); }
-    for (auto& c : old) free_class(c);
-    return DABPHY_OK;
+    return DABPHY_OK;                                        // (the copies out of `old` are done: its classes free their buffers here)
 }
 
 int dabphy_selftest_unit_twiddle(dabphy_handle* h, uint64_t* counts)
 {
     DeviceBind dev_(h);
     if (!h || !counts) return DABPHY_ERR_INVALID;
-    unsigned long long* d = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d, 2 * sizeof *d));
+    DevBuf buf; int r;
+    if ((r = dev_alloc(h, buf, 2 * sizeof(unsigned long long)))) return r;
+    unsigned long long* const d = buf.as<unsigned long long>();
     HIPCHK(h, hipMemsetAsync(d, 0, 2 * sizeof *d, h->stream));
     launch_selftest_unit_twiddle(d, h->stream);
     unsigned long long host[2];
     HIPCHK(h, hipMemcpyAsync(host, d, sizeof host, hipMemcpyDeviceToHost, h->stream));
-    const int r = sync(h);
-    (void)hipFree(d);
+    r = sync(h);
     for (int i = 0; i < 2; i++) counts[i] = host[i];
     return r;
 }
@@ -634,15 +541,15 @@ int dabphy_selftest_pair_exchange(dabphy_handle* h, uint64_t* counts)
 {
     DeviceBind dev_(h);
     if (!h || !counts) return DABPHY_ERR_INVALID;
-    unsigned* d = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d, 2 * sizeof *d));
+    DevBuf buf; int r;
+    if ((r = dev_alloc(h, buf, 2 * sizeof(unsigned)))) return r;
+    unsigned* const d = buf.as<unsigned>();
     HIPCHK(h, hipMemsetAsync(d, 0, 2 * sizeof *d, h->stream));
     launch_selftest_pair_exchange(d, h->stream);
     launch_selftest_half_exchange(d, h->stream);                 // ... and the forms of the two-code-words-per-wavefront kernel (same counters)
     unsigned host[2];
     HIPCHK(h, hipMemcpyAsync(host, d, sizeof host, hipMemcpyDeviceToHost, h->stream));
-    const int r = sync(h);
-    (void)hipFree(d);
+    r = sync(h);
     for (int i = 0; i < 2; i++) counts[i] = host[i];
     return r;
 }
@@ -651,14 +558,14 @@ int dabphy_selftest_div127(dabphy_handle* h, uint64_t* counts)
 {
     DeviceBind dev_(h);
     if (!h || !counts) return DABPHY_ERR_INVALID;
-    unsigned long long* d = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d, 3 * sizeof *d));
+    DevBuf buf; int r;
+    if ((r = dev_alloc(h, buf, 3 * sizeof(unsigned long long)))) return r;
+    unsigned long long* const d = buf.as<unsigned long long>();
     HIPCHK(h, hipMemsetAsync(d, 0, 3 * sizeof *d, h->stream));
     launch_selftest_div127(d, h->stream);
     unsigned long long host[3];
     HIPCHK(h, hipMemcpyAsync(host, d, sizeof host, hipMemcpyDeviceToHost, h->stream));
-    const int r = sync(h);
-    (void)hipFree(d);
+    r = sync(h);
     for (int i = 0; i < 3; i++) counts[i] = host[i];
     return r;
 }
@@ -690,8 +597,8 @@ int dabphy_time_demod(dabphy_handle* h, const float* frames, uint32_t n_src, uin
     a.tab = h->tab; a.iq = h->iq.as<cf32>(); a.iq_stride = per * n_frames; a.ring = (int64_t)(per * n_frames);
     a.desc = h->desc.as<FrameDesc>(); a.n_frames = (int)n_frames; a.chunk_len = h->cfg.demod_chunk; a.mix = mix;
     a.soft = h->soft.as<int8_t>(); a.soft_ring = (int)n_frames; a.con = nullptr; a.prs_mag = nullptr;
-    hipEvent_t e0, e1;
-    HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
+    ScopedEvent e0, e1;
+    HIPCHK(h, e0.create()); HIPCHK(h, e1.create());
     launch_demod(a, (int)n_ens, h->stream);                       // warm-up
     HIPCHK(h, hipEventRecord(e0, h->stream));
     for (uint32_t i = 0; i < iters; i++) launch_demod(a, (int)n_ens, h->stream);
@@ -699,7 +606,6 @@ int dabphy_time_demod(dabphy_handle* h, const float* frames, uint32_t n_src, uin
     HIPCHK(h, hipEventSynchronize(e1));
     float t = 0; HIPCHK(h, hipEventElapsedTime(&t, e0, e1));
     *ms = t / iters;
-    HIPCHK(h, hipEventDestroy(e0)); HIPCHK(h, hipEventDestroy(e1));
     return sync(h);
 }
 
@@ -710,26 +616,17 @@ int dabphy_time_copy(dabphy_handle* h, uint64_t bytes, uint32_t blocks_per_cu, u
     hipDeviceProp_t p;
     HIPCHK(h, hipGetDeviceProperties(&p, h->cfg.device));
     const int blocks = p.multiProcessorCount * (int)(blocks_per_cu ? blocks_per_cu : 4);
-    void *src = nullptr, *dst = nullptr;
-    if (hipMalloc(&src, bytes) != hipSuccess) { h->err = "hipMalloc failed (copy source)"; return DABPHY_ERR_NOMEM; }
-    if (hipMalloc(&dst, bytes) != hipSuccess) { (void)hipFree(src); h->err = "hipMalloc failed (copy destination)"; return DABPHY_ERR_NOMEM; }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipMemsetAsync(src, 1, bytes, h->stream);
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    float t = 0;
-    if (e == hipSuccess) {
-        for (int w = 0; w < 3; w++) launch_copy_f4(src, dst, bytes / 16, blocks, h->stream);      // clocks up, pages touched
-        e = hipEventRecord(e0, h->stream);
-        for (uint32_t i = 0; i < iters; i++) launch_copy_f4(src, dst, bytes / 16, blocks, h->stream);
-        if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(src); (void)hipFree(dst);
-    if (e != hipSuccess) { h->err = std::string("dabphy_time_copy: ") + hipGetErrorString(e); return DABPHY_ERR_HIP; }
+    DevBuf src, dst; int r;
+    if ((r = dev_alloc(h, src, bytes)) || (r = dev_alloc(h, dst, bytes))) return r;
+    ScopedEvent e0, e1;
+    HIPCHK(h, hipMemsetAsync(src.p, 1, bytes, h->stream));
+    HIPCHK(h, e0.create()); HIPCHK(h, e1.create());
+    for (int w = 0; w < 3; w++) launch_copy_f4(src.p, dst.p, bytes / 16, blocks, h->stream);      // clocks up, pages touched
+    HIPCHK(h, hipEventRecord(e0, h->stream));
+    for (uint32_t i = 0; i < iters; i++) launch_copy_f4(src.p, dst.p, bytes / 16, blocks, h->stream);
+    HIPCHK(h, hipEventRecord(e1, h->stream));
+    HIPCHK(h, hipEventSynchronize(e1));
+    float t = 0; HIPCHK(h, hipEventElapsedTime(&t, e0, e1));
     *gbytes_per_s = (float)(2.0 * (double)(bytes / 16 * 16) * iters / ((double)t * 1e-3) / 1e9);
     return sync(h);
 }
@@ -752,8 +649,8 @@ int dabphy_time_viterbi(dabphy_handle* h, uint32_t nbits, uint32_t n_codewords, 
     }
     LinGatherArgs g{}; g.in = h->in8.as<int8_t>(); g.in_stride = stride; g.map = nullptr; g.c = c;
     VitArgs v{}; v.c = c; v.prbs_words = h->d_prbs_words;
-    hipEvent_t e0, e1, e2;
-    HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1)); HIPCHK(h, hipEventCreate(&e2));
+    ScopedEvent e0, e1, e2;
+    HIPCHK(h, e0.create()); HIPCHK(h, e1.create()); HIPCHK(h, e2.create());
     launch_lin_gather(g, h->stream); launch_viterbi(v, h->stream);
     float tg = 0, tv = 0;
     for (uint32_t i = 0; i < iters; i++) {
@@ -767,7 +664,6 @@ int dabphy_time_viterbi(dabphy_handle* h, uint32_t nbits, uint32_t n_codewords, 
         tg += a; tv += b;
     }
     *ms_gather = tg / iters; *ms_decode = tv / iters;
-    HIPCHK(h, hipEventDestroy(e0)); HIPCHK(h, hipEventDestroy(e1)); HIPCHK(h, hipEventDestroy(e2));
     return sync(h);
 }
 
@@ -791,22 +687,18 @@ int dabphy_time_fused_msc(dabphy_handle* h, uint32_t iters, float* ms)
     const auto& P = h->fplan;
     if (!P.valid || !P.launched || P.buf_gen != h->buf_gen || P.args.n_work == 0) { h->err = "no batch has been decoded by the fused kernel with the present buffers"; return DABPHY_ERR_STATE; }
     HIPCHK(h, hipDeviceSynchronize());                       // alone on the device: nothing of the pipeline beside it
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(h, hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); h->err = "hipEventCreate failed"; return DABPHY_ERR_HIP; }
+    ScopedEvent e0, e1;
+    HIPCHK(h, e0.create()); HIPCHK(h, e1.create());
     const FusedSplit sp{h->tb_no_walkers ? nullptr : h->tb_stream, h->ev_tb_fork, h->ev_tb_join};
     auto again = [&]() { if (P.use_sp) launch_sp(P.args, P.sp_two, P.sp_variant, h->stream); else launch_viterbi_fused(P.args, P.variant, P.n_slots, h->stream, P.args.done ? &sp : nullptr); };
     again();                                                                  // (same inputs, same outputs: the launch is idempotent)
-    hipError_t e = hipEventRecord(e0, h->stream);
+    HIPCHK(h, hipEventRecord(e0, h->stream));
     // (split traceback: the launch forks a second stream off and joins it through two events the NEXT launch records again -- the stream
     // is drained between launches so that no wait is pending on an event when it is re-recorded; ~20 us per launch in the figure)
-    for (uint32_t i = 0; i < iters; i++) { again(); if (P.args.done && e == hipSuccess) e = hipStreamSynchronize(h->stream); }
-    if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    float t = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (e != hipSuccess) { h->err = std::string("dabphy_time_fused_msc: ") + hipGetErrorString(e); return DABPHY_ERR_HIP; }
+    for (uint32_t i = 0; i < iters; i++) { again(); if (P.args.done) HIPCHK(h, hipStreamSynchronize(h->stream)); }
+    HIPCHK(h, hipEventRecord(e1, h->stream));
+    HIPCHK(h, hipEventSynchronize(e1));
+    float t = 0; HIPCHK(h, hipEventElapsedTime(&t, e0, e1));
     *ms = t / iters;
     return sync(h);
 }

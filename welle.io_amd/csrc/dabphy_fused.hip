@@ -170,18 +170,12 @@ int fused_plan(dabphy_handle* h, uint32_t F, bool want_fic)
         if (tb_split) {
             if ((r = ensure(h, h->fused_done, (work.size() + 2) * sizeof(uint32_t)))) return r;
             if (!h->tb_stream) {
-                HIPCHK(h, hipStreamCreateWithFlags(&h->tb_stream, hipStreamNonBlocking));
-                HIPCHK(h, hipEventCreateWithFlags(&h->ev_tb_fork, hipEventDisableTiming));
-                HIPCHK(h, hipEventCreateWithFlags(&h->ev_tb_join, hipEventDisableTiming));
+                if ((r = new_stream(h, &h->tb_stream)) || (r = new_event(h, &h->ev_tb_fork)) || (r = new_event(h, &h->ev_tb_join))) return r;
             }
         }
         if ((r = ensure(h, h->fused_cls, cls.size() * sizeof(FusedClass)))) return r;
         if ((r = ensure(h, h->fused_work, work.size() * sizeof(uint32_t)))) return r;
-        if (!h->d_fused_next) {
-            void* p = nullptr;
-            if (hipMalloc(&p, sizeof(uint32_t)) != hipSuccess) { h->err = "hipMalloc failed (work cursor)"; return DABPHY_ERR_NOMEM; }
-            h->owned.push_back(p); h->d_fused_next = reinterpret_cast<uint32_t*>(p);
-        }
+        if (!h->d_fused_next && (r = device_block(h, &h->d_fused_next, 1))) return r;
     }
     const bool same_cls = P.valid && P.buf_gen == h->buf_gen && P.host_cls.size() == cls.size() &&
                           (cls.empty() || !memcmp(P.host_cls.data(), cls.data(), cls.size() * sizeof(FusedClass)));
@@ -234,11 +228,7 @@ int sp_single_reserve(dabphy_handle* h, uint64_t n_cw, int nsteps)
     const uint64_t n_groups = (n_cw + 63) / 64;
     int r;
     if (n_groups > (uint64_t)SP_SINGLE_MAX_GROUPS) { h->err = "one-class state-parallel launch: too many groups"; return DABPHY_ERR_INVALID; }
-    if (!h->h_sp1) {
-        void* p = nullptr;
-        if (hipHostMalloc(&p, sizeof(FusedClass) + SP_SINGLE_MAX_GROUPS * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { h->err = "hipHostMalloc failed (one-class staging)"; return DABPHY_ERR_NOMEM; }
-        h->h_sp1 = p;
-    }
+    if (!h->h_sp1 && (r = pinned_alloc(h, sizeof(FusedClass) + SP_SINGLE_MAX_GROUPS * sizeof(uint32_t), &h->h_sp1))) return r;
     const size_t cells = ((size_t)nsteps / 30 + 1) * 32;                 // (per code word: the same for either kernel)
     if ((r = ensure(h, h->sp1_cls, sizeof(FusedClass)))) return r;
     if ((r = ensure(h, h->sp1_work, SP_SINGLE_MAX_GROUPS * sizeof(uint32_t)))) return r;

@@ -247,9 +247,8 @@ int dabphy_msc_drain_begin(dabphy_handle* h, dabphy_msc_desc* desc, uint32_t des
         // it overlaps completely (10.07 ms).  A handle that is fed through dabphy_stream_write_raw_async keeps that stream for its
         // host-to-device transfers and drains on one of its own.
         if (h->s_enqueued == 0 && !(h->stream_layout & 8)) h->drain_stream = h->copy_stream;
-        else HIPCHK(h, hipStreamCreateWithFlags(&h->drain_stream, hipStreamNonBlocking));
-        HIPCHK(h, hipEventCreateWithFlags(&h->ev_drain_done, hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&h->ev_drain_staged, hipEventDisableTiming));
+        else if ((r = new_stream(h, &h->drain_stream))) return r;
+        if ((r = new_event(h, &h->ev_drain_done)) || (r = new_event(h, &h->ev_drain_staged))) return r;
     }
     // (dabphy_process has returned: the class outputs are final, nothing on the main stream is pending.)  The outputs first go to a
     // staging area in HBM -- a device copy on the main stream, tens of microseconds for a hundred MB, ordered in front of the next batch's

@@ -7,6 +7,8 @@
 //   dabphy_superframes.hip  Reed-Solomon seams and the DAB+ superframe filter
 //   dabphy_mp2.hip          classic DAB (MP2) services: audio kinds, the MP2 frame check and its unit entry
 //   dabphy_getters.hip      everything a caller reads back after a batch, profiling, TII
+// Ownership: a device buffer (DevBuf) owns itself and is freed by its destructor; streams, events and page-locked blocks are created
+// through new_stream / new_event / pinned_alloc below and nowhere else, which register them with the handle for dabphy_destroy.
 #pragma once
 #define DABPHY_BUILDING_LIBRARY          // (the exported symbol `dabphy_create` is the frozen round-3 entry point here, not the header's inline)
 #include "../../include/dabphy.h"
@@ -38,11 +40,17 @@ inline bool debug_env(const char* name)
 #endif
 }
 
+// A device allocation and its owner: move-only (a move leaves the source empty), freed by the destructor; dev_alloc / ensure fill it
 struct DevBuf {
     void* p = nullptr; size_t cap = 0;
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~DevBuf() { release(); }
+    void release() { if (p) { hipError_t e = hipFree(p); (void)e; p = nullptr; cap = 0; } }
 };
-
 
 constexpr int HIST_CAP = 64;     // window searches remembered per ensemble for the sLevel replay
 // superframe filter launches (dabphy_superframes.hip): a class to walk and which of its pairs (DEVICE list; nullptr: all of them)
@@ -68,7 +76,8 @@ struct dabphy_handle {
     DevBuf fsym, fdec;                      // Viterbi scratch of the FIC class (it decodes beside the MSC classes on aux_stream)
     RxState* d_state = nullptr;       // [n_ensembles] synchroniser state
     DecState* d_dec = nullptr;        // [n_ensembles] decoder state
-    std::vector<void*> owned;
+    std::vector<DevBuf> owned;        // blocks of fixed size that live as long as the handle (device_block: tables, state, flags)
+    std::vector<hipStream_t> streams; std::vector<hipEvent_t> events; std::vector<void*> pinned;   // what new_stream / new_event / pinned_alloc created, each once (an alias such as fic_stream = aux_stream is not registered again): dabphy_destroy releases them
 
     // ---- streaming receiver (dabphy_stream_* / dabphy_process)
     // One protection class of the batch: the (ensemble, sub-channel) pairs of ALL ensembles that share a protection profile -- every
@@ -120,8 +129,7 @@ struct dabphy_handle {
     static constexpr int N_DESC = 3;    // descriptor buffers: the batch being decoded + up to two synchronised ahead
     DevBuf s_desc2[N_DESC], s_cir2[N_DESC], s_soft, s_con, s_mag, s_snr, s_fib, s_ok;
     int stream_layout = 1;                          // experiments: bit 0 placeholder streams, bit 1 FIC work on the auxiliary stream, bit 3 the bulk drain on a stream of its own even when nothing is ingested asynchronously, bit 4 the SNR kernels on the main stream in front of the decoder (no gain: profiles/r06_step_variants.txt)
-    std::vector<hipStream_t> placeholder_streams;   // created in front of the handle's own, never used (dabphy_create_v2: stream placement)
-    hipStream_t sync_stream = nullptr; hipEvent_t ev_sync_done = nullptr;
+    hipStream_t sync_stream = nullptr;
     hipStream_t aux_stream = nullptr; hipEvent_t ev_demod_done = nullptr, ev_fic_done = nullptr, ev_chain_gate = nullptr;
     hipStream_t fic_stream = nullptr; hipEvent_t ev_aux_done = nullptr;     // FIB CRC + FIC ratio behind a fused launch; end of the auxiliary stream's work of a batch
     // fused decode (k_viterbi_fused): every class of the batch (and the FIC) in one launch.  The plan = which build, which classes, the
@@ -218,26 +226,76 @@ struct DeviceBind {
 #define HIPCHK(h, call)                                                                                   \
     do { hipError_t e_ = (call); if (e_ != hipSuccess) { (h)->err = std::string(#call) + ": " + hipGetErrorString(e_); return DABPHY_ERR_HIP; } } while (0)
 
-inline int ensure(dabphy_handle* h, DevBuf& b, size_t bytes)
+// exactly `bytes` of device memory into an EMPTY buffer (the one place the library allocates device memory)
+inline int dev_alloc(dabphy_handle* h, DevBuf& b, size_t bytes)
 {
-    if (bytes <= b.cap) return 0;
-    if (b.p) { hipError_t e = hipFree(b.p); (void)e; b.p = nullptr; b.cap = 0; }
-    h->buf_gen++;
-    bytes = (bytes + 4095) & ~(size_t)4095;
     if (hipMalloc(&b.p, bytes) != hipSuccess) { h->err = "hipMalloc failed (" + std::to_string(bytes) + " bytes)"; b.p = nullptr; return DABPHY_ERR_NOMEM; }
     b.cap = bytes;
     return 0;
 }
 
-template <typename T> int upload_const(dabphy_handle* h, T** dst, const std::vector<T>& src)
+// grow-only scratch: contents are not preserved; whatever names the old address is out of date (buf_gen)
+inline int ensure(dabphy_handle* h, DevBuf& b, size_t bytes)
 {
-    void* p = nullptr;
-    if (hipMalloc(&p, src.size() * sizeof(T)) != hipSuccess) { h->err = "hipMalloc(table) failed"; return DABPHY_ERR_NOMEM; }
-    h->owned.push_back(p);
-    HIPCHK(h, hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    *dst = reinterpret_cast<T*>(p);
+    if (bytes <= b.cap) return 0;
+    b.release();
+    h->buf_gen++;
+    return dev_alloc(h, b, (bytes + 4095) & ~(size_t)4095);
+}
+
+// n elements that live as long as the handle (h->owned)
+template <typename T> int device_block(dabphy_handle* h, T** dst, size_t n, bool zero = false)
+{
+    DevBuf b; int r;
+    if ((r = dev_alloc(h, b, n * sizeof(T)))) return r;
+    *dst = b.as<T>();
+    h->owned.push_back(std::move(b));
+    if (zero) HIPCHK(h, hipMemset(*dst, 0, n * sizeof(T)));
     return 0;
 }
+
+template <typename T> int upload_const(dabphy_handle* h, T** dst, const std::vector<T>& src)
+{
+    int r;
+    if ((r = device_block(h, dst, src.size()))) return r;
+    HIPCHK(h, hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// Streams (non-blocking; high_priority: the device's greatest), events (without timing unless asked) and page-locked host blocks of a
+// handle: created here, registered for dabphy_destroy.  *out stays null on failure.
+inline int new_stream(dabphy_handle* h, hipStream_t* out, bool high_priority = false)
+{
+    int lo = 0, hi = 0;
+    if (high_priority && hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) hi = 0;
+    hipStream_t s = nullptr;
+    if ((high_priority ? hipStreamCreateWithPriority(&s, hipStreamNonBlocking, hi) : hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess) { h->err = "hipStreamCreate failed"; return DABPHY_ERR_HIP; }
+    h->streams.push_back(s); *out = s;
+    return 0;
+}
+inline int new_event(dabphy_handle* h, hipEvent_t* out, bool timing = false)
+{
+    hipEvent_t e = nullptr;
+    if ((timing ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableTiming)) != hipSuccess) { h->err = "hipEventCreate failed"; return DABPHY_ERR_HIP; }
+    h->events.push_back(e); *out = e;
+    return 0;
+}
+template <typename T> int pinned_alloc(dabphy_handle* h, size_t bytes, T** out)
+{
+    void* p = nullptr;
+    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { h->err = "hipHostMalloc failed (" + std::to_string(bytes) + " bytes)"; return DABPHY_ERR_NOMEM; }
+    h->pinned.push_back(p); *out = static_cast<T*>(p);
+    return 0;
+}
+
+// an event of one timing run: destroyed when the driver returns, whichever way
+struct ScopedEvent {
+    hipEvent_t e = nullptr;
+    ScopedEvent() = default; ScopedEvent(const ScopedEvent&) = delete; ScopedEvent& operator=(const ScopedEvent&) = delete;
+    hipError_t create() { return hipEventCreate(&e); }
+    ~ScopedEvent() { if (e) { hipError_t r = hipEventDestroy(e); (void)r; } }
+    operator hipEvent_t() const { return e; }
+};
 
 // Exact batch mode's second pass is armed whenever a coarse-corrector decision can have seen a FIC ratio older than the reference's
 // (ofdm-processor.cpp:397-409: the ratio of the PREVIOUS frame): batches of several frames, and ONE frame per call too when the
@@ -283,7 +341,6 @@ DABPHY_INTERNAL int prepare_mp2(dabphy_handle* h, uint32_t F);
 DABPHY_INTERNAL int launch_mp2_pass(dabphy_handle* h, uint32_t F);
 DABPHY_INTERNAL size_t mp2_stride();
 DABPHY_INTERNAL int upload_pairs(dabphy_handle* h, dabphy_handle::MscClass& cls);
-DABPHY_INTERNAL void free_class(dabphy_handle::MscClass& c);
 DABPHY_INTERNAL int launch_superframe_stats(dabphy_handle* h, hipStream_t st = nullptr, const FrameDesc* desc = nullptr, uint32_t n_frames = 0);
 DABPHY_INTERNAL int launch_deferred_superframes(dabphy_handle* h);       // dabphy_set_auto_superframes(2): the pending pass of the previous batch, on rs_stream
 DABPHY_INTERNAL int flush_deferred_superframes(dabphy_handle* h);        // ... now, and wait for it

@@ -98,7 +98,7 @@ int launch_mp2_pass(dabphy_handle* h, uint32_t F)
         a.events = c.mp2_ev.as<Mp2Event>(); a.ev_cap = mp2_ev_cap(F); a.n_events = c.mp2_n.as<int32_t>();
         a.frame_errors = c.mp2_err.as<int32_t>(); a.first_unverified = c.mp2_fu.as<int32_t>(); a.stats = h->mp2_stats.as<int32_t>();
         if (h->profiling && first) {
-            if (!h->ev_mp2[0]) for (int i = 0; i < 2; i++) HIPCHK(h, hipEventCreate(&h->ev_mp2[i]));
+            if (!h->ev_mp2[0]) for (int i = 0; i < 2; i++) { const int rc = new_event(h, &h->ev_mp2[i], true); if (rc) return rc; }
             HIPCHK(h, hipEventRecord(h->ev_mp2[0], h->stream));
         }
         launch_mp2(a, c.n_mp2, h->stream);

@@ -265,7 +265,7 @@ int dabphy_process(dabphy_handle* h, uint32_t n_frames)
         else { const FusedSplit sp{h->tb_no_walkers ? nullptr : h->tb_stream, h->ev_tb_fork, h->ev_tb_join}; launch_viterbi_fused(fa, h->fplan.variant, h->fplan.n_slots, h->stream, fa.done ? &sp : nullptr); }
         mark(dabphy_handle::ST_MSC_VITERBI, true);
         if (fa.done) {
-            if (!h->h_tb_gave_up) { void* p = nullptr; HIPCHK(h, hipHostMalloc(&p, sizeof(uint32_t), hipHostMallocDefault)); h->h_tb_gave_up = reinterpret_cast<uint32_t*>(p); }
+            if (!h->h_tb_gave_up) { const int rc = pinned_alloc(h, sizeof(uint32_t), &h->h_tb_gave_up); if (rc) return rc; }
             launch_copy_out(fa.done + fa.n_work + 1, h->h_tb_gave_up, sizeof(uint32_t), h->stream);
         }
         if (fic_fused) HIPCHK(h, hipEventRecord(h->ev_fused_done, h->stream));

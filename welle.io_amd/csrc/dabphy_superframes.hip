@@ -28,11 +28,7 @@ int prepare_superframes(dabphy_handle* h, uint32_t F)
     if ((r = ensure(h, h->sf_bytes, bytes))) return r;
     if ((r = ensure(h, h->sf_accept, sizeof(int32_t) * pairs))) return r;
     if ((r = ensure(h, h->sf_batch, SF_BATCH_BYTES))) return r;
-    if (!h->h_sf_batch) {
-        void* p = nullptr;
-        if (hipHostMalloc(&p, SF_BATCH_BYTES, hipHostMallocDefault) != hipSuccess) { h->err = "hipHostMalloc failed (superframe filter staging)"; return DABPHY_ERR_NOMEM; }
-        h->h_sf_batch = p;
-    }
+    if (!h->h_sf_batch && (r = pinned_alloc(h, SF_BATCH_BYTES, &h->h_sf_batch))) return r;
     if (!h->sf_gf.p) {
         // GF(256) of RS(120,110), generator polynomial 0x11D (init_rs.h:48-60): alpha_to[256], index_of[256]  (built once, thread-safely:
         // the node receiver creates its handles from several host threads)
@@ -265,7 +261,8 @@ int launch_deferred_superframes(dabphy_handle* h)
     // behind the demod kernel instead of beside it: profiles/r06_step_variants.txt)
     if (!h->rs_stream) {
         h->rs_stream = h->aux_stream;
-        HIPCHK(h, hipEventCreateWithFlags(&h->ev_rs_done, hipEventDisableTiming));
+        const int rc = new_event(h, &h->ev_rs_done);
+        if (rc) return rc;
     }
     int r;
     if ((r = launch_superframe_stats(h, h->rs_stream, h->sf_def_desc, h->sf_def_frames))) return r;
