@@ -388,7 +388,11 @@ int dabphy_rs_superframes(dabphy_handle* h, uint8_t* sf, uint32_t s_per_sf, uint
  * position of every ensemble that has one.
  * first_cif[b]: CIF slot of this batch (0..4*n_frames-1, may be negative) where ensemble b's first superframe
  * starts -- the alignment SuperframeFilter::CheckSync (dabplus_decoder.cpp:171-215) finds on the host.  Only
- * superframes lying entirely inside the batch are decoded.  corrected / uncorrectable (may be NULL): per ensemble sums. */
+ * superframes lying entirely inside rows [first_valid, n_rows) of their (ensemble, sub-channel) pair (dabphy_get_msc) are decoded: one
+ * that touches a row outside them is neither counted nor written.  Positions whose audio kind is DABPHY_AUDIO_MP2
+ * (dabphy_set_audio_kinds_ensemble) are left out, their bytes stay as they are: with subch_index < 0 silently, with an index that is an
+ * MP2 service in some ensembles only in those, and with one that is an MP2 service in every ensemble that has it the call returns
+ * DABPHY_ERR_INVALID.  corrected / uncorrectable (may be NULL): per ensemble sums. */
 int dabphy_rs_decode_msc(dabphy_handle* h, int32_t subch_index, const int32_t* first_cif, int32_t* corrected,
                          int32_t* uncorrectable);
 

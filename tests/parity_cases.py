@@ -4,6 +4,7 @@ report (north star: floats within 1e-5), stated where it is used."""
 import numpy as np
 
 import refapi as R
+import sf_cases as S
 from welle_io_amd import synth
 
 
@@ -318,11 +319,13 @@ def check_live_raw_vs_oracle(d_factory, fmt, nf=9, seed=5, snr_db=18, cfo=-35, a
 
 # ---- DAB+ superframe filter on the device vs the oracle's (itself pinned to the real SuperframeFilter)
 def check_superframes_vs_oracle(d_factory, F=3, nf=16, snr_db=5.0, seed=12, B=2, damage=True, auto_modes=(False, True), cfo=20, stats=None, min_synced=1,
-                                ensemble=None, pick=(1, 6), damage_q=(6, 8)):
+                                ensemble=None, pick=(1, 6), damage_q=(6, 8), payload_fn=None):
     """superframes straddle the batches (12 logical frames per batch, 5 per superframe); the noise level makes the Viterbi
     output carry byte errors for Reed-Solomon to correct (no loss of lock: batch mode and the reference drop different
     frames then), and the transmitter damages some superframes beyond repair: a broken access unit, more byte errors than
-    RS(120,110) corrects, a Fire-code hit that costs the synchronisation"""
+    RS(120,110) corrects, a Fire-code hit that costs the synchronisation.  payload_fn: another payload for the whole ensemble instead
+    (the caller then asserts on its own what it meant to cover; stats gets the oracle's events per picked sub-channel and the first
+    logical frame the oracle emitted)"""
     base = synth.dabplus_payload_fn(80, seed)
 
     def payload(sc, r):
@@ -337,7 +340,7 @@ def check_superframes_vs_oracle(d_factory, F=3, nf=16, snr_db=5.0, seed=12, B=2,
                 for j in range(4, 10): data[j * (sc.bitrate // 8)] ^= 0x81           # header column uncorrectable -> Fire code fails -> window slides
         return bytes(data)
     # ensemble: the sub-channels of the multiplex (default: 18 x 64 kbit/s); pick: the ones the filter is checked on
-    x, tx = synth.make_stream(nf, snr_db=snr_db, cfo_hz=cfo, delay=50, return_tx=True, seed=seed, payload_fn=payload, subchs=ensemble)
+    x, tx = synth.make_stream(nf, snr_db=snr_db, cfo_hz=cfo, delay=50, return_tx=True, seed=seed, payload_fn=payload_fn or payload, subchs=ensemble)
     subs = [tx.subchs[i] for i in pick]
     o = R.orc_receiver_run(x, subchs=subs)
     d = d_factory(n_ensembles=B, max_frames=F, want_constellation=False)
@@ -364,6 +367,8 @@ def check_superframes_vs_oracle(d_factory, F=3, nf=16, snr_db=5.0, seed=12, B=2,
             frames = np.frombuffer(bytes(o["msc"][i]), np.uint8)
             frames = frames[:len(frames) // fb * fb].reshape(-1, fb)
             eo, so = R.orc_superframe_run(frames)
+            if stats is not None:
+                stats.setdefault("oracle_events", {})[i] = eo; stats.setdefault("oracle_frames", {})[i] = frames
             want = [e[1:] for e in eo]
             for b in range(B):
                 n = len(got[b][i])
@@ -377,7 +382,7 @@ def check_superframes_vs_oracle(d_factory, F=3, nf=16, snr_db=5.0, seed=12, B=2,
         # both ways through the filter were taken: batches whose attempts all synchronised were settled by the wide pass, the damaged
         # ones (and the first, which only fills the window) were walked frame by frame
         settled, tried = d.wide_superframe_stats()
-        assert tried > 0 and (0 < settled < tried if damage and nf >= 16 and damage_q == (6, 8) else settled <= tried), (settled, tried)
+        assert tried > 0 and (0 < settled < tried if damage and nf >= 16 and damage_q == (6, 8) and payload_fn is None else settled <= tried), (settled, tried)
         if stats is not None:
             stats["sf_wide"] = (settled, tried)
     finally:
@@ -404,6 +409,61 @@ def check_superframes_vs_oracle(d_factory, F=3, nf=16, snr_db=5.0, seed=12, B=2,
         finally:
             d.close()
     return got
+
+
+LAYOUT_RATES = (8, 24, 40, 72, 136, 384)
+
+
+def check_superframe_layouts(d_factory, F=3, nf=22, rates=LAYOUT_RATES, snr_db=5.0, seed=12, B=2, auto_modes=(False, True), need_rates=3):
+    """the filter through the stream on everything CheckSync distinguishes: one ensemble of DAB+ sub-channels of 8 .. 384 kbit/s at EEP
+    3-A (one to 48 code words per superframe: tail rounds of the eight-at-a-time syndrome pass, rows of three 8-byte words, the longest
+    row of the largest bucket) whose superframes follow sf_cases.schedule -- the four access-unit layouts, every rejection rule, access
+    units of two bytes and of one, byte errors within and beyond the RS capacity.  Events, corrected superframes and totals equal the
+    oracle's (check_superframes_vs_oracle); and, counted on the ORACLE's events, the stream really held what it was built to hold."""
+    subchs, cu = [], 0
+    for i, br in enumerate(rates):
+        sc = synth.SubchannelCfg(i + 1, cu, br, False, 3); subchs.append(sc); cu += sc.size_cu
+    assert cu <= 864
+    pay = S.payload_fn(80, seed)
+    stats = {}
+    check_superframes_vs_oracle(d_factory, F=F, nf=nf, snr_db=snr_db, seed=seed, B=B, auto_modes=auto_modes, stats=stats, ensemble=subchs,
+                                pick=tuple(range(len(subchs))), payload_fn=pay)
+    cov = superframe_layout_coverage(subchs, stats["oracle_events"], stats["oracle_frames"], pay)
+    for lay, brs in cov["layout_rates"].items():
+        assert len(brs) >= min(need_rates, len(rates)) and {min(rates), max(rates)} <= brs, "layout %s synchronised at %s kbit/s only" % (lay, sorted(brs))
+    assert cov["rejected"] == set(S.REJECTS), cov["rejected"]
+    assert cov["au2_ok"] >= 1 and cov["au1_failed"] >= 1, cov
+    settled, tried = stats["sf_wide"]
+    assert 0 < settled < tried, (settled, tried)
+    return cov
+
+
+def superframe_layout_coverage(subchs, events, frames, pay):
+    """what the oracle's filter made of a stream built by sf_cases.payload_fn: {layout: bit rates it synchronised at}, the reject
+    kinds whose superframe gave an unsynchronised attempt on the aligned window, access units of length 2 that passed and of length 1
+    that were counted as failed.  events[i] / frames[i]: oracle events and logical frames of sub-channel i"""
+    cov = dict(layout_rates={lay: set() for lay in S.LAYOUTS}, rejected=set(), au2_ok=0, au1_failed=0)
+    for i, sc in enumerate(subchs):
+        fr = frames[i]
+        # the transmitted logical frame the first received one is: the closest of the period (the channel leaves byte errors)
+        r0 = min(range(80), key=lambda r: int((np.frombuffer(pay(sc, r), np.uint8) != fr[0]).sum()))
+        assert int((np.frombuffer(pay(sc, r0), np.uint8) != fr[0]).sum()) <= len(fr[0]) // 4
+        for e in events[i]:
+            r = r0 + e[0]                                                      # transmitted frame that completed the window
+            if r % 5 != 4:
+                continue
+            layout, flags, au_lengths, reject, damage = S.schedule(sc.subch_id, (r % 80) // 5)
+            if e[3]:
+                lay = [k for k, v in S.LAYOUTS.items() if v[0] == e[5]][0]
+                if reject is None and e[6][0] == S.LAYOUTS[lay][1] and lay == tuple(layout):
+                    cov["layout_rates"][lay].add(sc.bitrate)
+                for a in range(e[5]):
+                    ln = e[6][a + 1] - e[6][a]
+                    cov["au2_ok"] += ln == 2 and bool(e[7] >> a & 1)
+                    cov["au1_failed"] += ln == 1 and not e[7] >> a & 1
+            elif reject is not None:
+                cov["rejected"].add(reject.partition(":")[0])
+    return cov
 
 
 MIXED_CFGS = [(1, 32, False, 1), (2, 128, False, 2), (3, 64, True, 3), (4, 48, False, 4), (5, 8, False, 3), (6, 192, False, 3), (7, 32, True, 1)]
@@ -1141,6 +1201,127 @@ def check_rs_random(d, n_sf=300, seed=77, s_per_sf=8):
         assert (int(corr[k]), bool(unc[k])) == (int(c), bool(u)), (k, int(corr[k]), int(unc[k]), c, u)
         n_unc += bool(u)
     assert n_unc > n_sf // 4 and max(weights) == 12          # the beyond-capacity paths were really taken
+
+
+def check_rs_directed(d, s, sets=None):
+    """RS(120,110) on words built to take the decoder's corner paths (tests/sf_cases.py: roots in the padding, miscorrections written in
+    full, errors at both ends of data and parity, zero data, S0 = 0, five and six errors in the same places), packed into superframes of
+    s columns; per set one superframe that mixes the classes across its columns, so that neighbouring lanes hold clean, corrected,
+    given-up and miscorrected words.  Bytes, corrected-symbol totals and verdicts equal the oracle's."""
+    sets = sets or S.directed_sets()
+    rng = np.random.RandomState(100 + s)
+    for name in sets:
+        sfs = np.concatenate([S.pack_columns(sets[name][0], s, rng), S.mixed_superframe(sets, name, s, rng)[None]])
+        out, corr, unc = d.rs_superframes(sfs, s)
+        for k in range(len(sfs)):
+            o, c, u = R.orc_rs_superframe(sfs[k])
+            assert np.array_equal(out[k], o), "%s, s = %d, superframe %d: corrected bytes differ at %s" % (name, s, k, np.nonzero(out[k] != o)[0][:8])
+            assert (int(corr[k]), bool(unc[k])) == (int(c), bool(u)), (name, s, k, int(corr[k]), int(unc[k]), c, u)
+
+
+RS_GEOMETRIES = {1: 300, 3: 171, 5: 77, 9: 57, 17: 31, 24: 21, 48: 11}      # s -> superframes: s * n is no multiple of 256 and more than one work-group
+
+
+RS_MSC_SERVICES = [(1, 64, "mp2"), (2, 32, "dab"), (3, 72, "dab"), (4, 64, "dab"), (5, 8, "dab"), (6, 64, "mp2")]
+RS_MSC_LISTS = ([0, 1, 2, 5], [3, 2, 4])       # positions -> services: position 0 is MP2 in ensemble 0 and DAB+ in ensemble 1, position 3 MP2 wherever it exists
+
+
+def check_rs_decode_msc(d_factory, F=3, nf=20, snr_db=4.5, seed=23):
+    """dabphy_rs_decode_msc (k_rs_msc: Reed-Solomon in place on the class outputs of the last batch, superframes addressed across
+    logical-frame rows) against the oracle composed over the rows read BEFORE the call: groups of five rows from first_cif[b] in steps of
+    five count iff they lie inside [first_valid, n_rows) of their pair; orc_rs_superframe on such a group gives the bytes after the call
+    and the per-ensemble sums; every other row -- the rows the header calls undefined included -- and every MP2 service stays as it was.
+    Two ensembles with different lists and rates of 8 .. 72 kbit/s, byte errors from the channel, a frame of silence in ensemble 1 (its
+    n_rows then falls below 4 F), the first batches (first_valid > 0), with subch_index = -1 and with every single position; the MP2
+    frame check run after the Reed-Solomon call gives what it gives without one."""
+    from welle_io_amd import capi
+    T_F = 196608
+    subchs, cu = [], 0
+    for sid, br, _ in RS_MSC_SERVICES:
+        sc = synth.SubchannelCfg(sid, cu, br, False, 3); subchs.append(sc); cu += sc.size_cu
+    dab = synth.dabplus_payload_fn(80, seed); mp2 = synth.mp2_payload_fn(80, seed)
+    kind_of = {sid: k for sid, _, k in RS_MSC_SERVICES}
+
+    def payload(sc, r):
+        return bytes(mp2(sc, r)) if kind_of[sc.subch_id] == "mp2" else dab(sc, r)
+    x = synth.make_stream(nf, snr_db=snr_db, cfo_hz=20, delay=50, seed=seed, payload_fn=payload, subchs=subchs)
+    x2 = x.copy(); x2[7 * T_F + 50000:8 * T_F + 120000] = 0
+    lists = [[subchs[i] for i in l] for l in RS_MSC_LISTS]
+    kinds = [[capi.AUDIO_MP2 if kind_of[s.subch_id] == "mp2" else capi.AUDIO_DABPLUS for s in l] for l in lists]
+    B = 2
+    seen = dict(groups=0, corrected=0, uncorrectable=0, skipped_front=0, skipped_back=0, short_rows=0, first_valid=0, changed=0)
+
+    def run(mode):
+        """mode: None = no Reed-Solomon call, -1 = every position, "each" = the positions one after the other, batch by batch -> MP2 totals per batch"""
+        d = d_factory(n_ensembles=B, max_frames=F, want_constellation=False, disable_coarse=True)
+        mp2_tot = []
+        try:
+            d.stream_upload(np.stack([x, x2]))
+            for b in range(B):
+                d.set_subchannels_ensemble(b, [(s.subch_id, s.start_cu, s.size_cu, d.protection_eep(s.bitrate, s.profile_b, s.level)) for s in lists[b]])
+                d.set_audio_kinds_ensemble(b, kinds[b])
+            d.set_auto_mp2(False)
+            emitted = [0] * B; r0 = [None] * B
+            for k in range((nf + F - 1) // F + 1):
+                d.process(F)
+                if not (d.frame_info()["valid"] == 1).any():
+                    break
+                before = [[d.msc_ensemble(b, i) for i in range(len(lists[b]))] for b in range(B)]
+                first_cif = np.zeros(B, np.int32)
+                for b in range(B):
+                    rows, fv, nr = before[b][1]                                # (a DAB+ service in both lists) where the ensemble's superframes start
+                    if r0[b] is None and nr > fv:
+                        r0[b] = min(range(80), key=lambda r: int((np.frombuffer(payload(lists[b][1], r), np.uint8) != rows[fv]).sum()))
+                    al = fv + (-((r0[b] or 0) + emitted[b])) % 5
+                    first_cif[b] = al - 5 * ((k + b) % 3)                     # negative starts, and starts inside the rows in front of first_valid
+                    emitted[b] += max(0, nr - fv)
+                    seen["short_rows"] += nr < 4 * F and nr > 0; seen["first_valid"] += 0 < fv < nr
+                if mode is not None:
+                    idx = -1 if mode == -1 else k % 3
+                    corr, unc = d.rs_decode_msc(idx, first_cif)
+                    want_c = np.zeros(B, np.int64); want_u = np.zeros(B, np.int64)
+                    for b in range(B):
+                        for i in range(len(lists[b])):
+                            rows, fv, nr = before[b][i]
+                            want = rows.copy()
+                            if kinds[b][i] == capi.AUDIO_DABPLUS and idx in (-1, i):
+                                for g in range(int(first_cif[b]), 4 * F - 4, 5):
+                                    if g < fv or g + 5 > nr:
+                                        seen["skipped_front"] += 0 <= g < fv; seen["skipped_back"] += g >= fv and g + 5 > nr
+                                        continue
+                                    o, c, u = R.orc_rs_superframe(rows[g:g + 5].reshape(-1))
+                                    want[g:g + 5] = o.reshape(5, -1); want_c[b] += c; want_u[b] += u
+                                    seen["groups"] += 1; seen["corrected"] += c; seen["uncorrectable"] += u
+                            after = d.msc_ensemble(b, i)[0]
+                            seen["changed"] += int((want != rows).sum())
+                            bad = np.nonzero((after != want).any(1))[0]
+                            assert not len(bad), "batch %d, ensemble %d, position %d (%s, %d kbit/s), subch_index %d: rows %s differ (rows [%d, %d) are the batch's, first_cif %d)%s" % (
+                                k, b, i, "MP2" if kinds[b][i] else "DAB+", lists[b][i].bitrate, idx, list(bad), fv, nr, first_cif[b],
+                                "" if (after[bad] != rows[bad]).any() else " -- left as they were")
+                    assert (list(corr), list(unc)) == (list(want_c), list(want_u)), "batch %d, subch_index %d: corrected %s uncorrectable %s, the oracle on the batch's own superframes gives %s %s" % (
+                        k, idx, list(corr), list(unc), list(want_c), list(want_u))
+                    if k == 2:
+                        # a position that is an MP2 service wherever it exists, and one that no ensemble has
+                        for bad_idx in (3, 7):
+                            try:
+                                d.rs_decode_msc(bad_idx, first_cif)
+                            except capi.DabPhyError as e:
+                                assert "status" in str(e)
+                            else:
+                                raise AssertionError("subch_index %d accepted" % bad_idx)
+                mp2_tot.append(d.mp2_stats().copy())
+        finally:
+            d.close()
+        return np.array(mp2_tot)
+    plain = run(None)
+    assert plain[:, 0, 0].sum() > 0, plain.sum(0)                     # ensemble 0's MP2 services: frames were checked
+    for mode in (-1, "each"):
+        got = run(mode)
+        assert np.array_equal(got, plain), "the MP2 frame check after dabphy_rs_decode_msc(%s) differs from a run without: %s / %s" % (mode, got.sum(0).tolist(), plain.sum(0).tolist())
+    # the stream held what the check is about
+    assert seen["groups"] >= 20 and seen["corrected"] > 0 and seen["changed"] > 0 and seen["uncorrectable"] > 0, seen
+    assert seen["skipped_front"] > 0 and seen["skipped_back"] > 0 and seen["short_rows"] > 0 and seen["first_valid"] > 0, seen
+    return seen
 
 
 def check_wide_sync(d_factory, F=6, nf=34, pipeline_sync=False, cfo=37.0, snr_db=22, B=2):

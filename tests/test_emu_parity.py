@@ -87,3 +87,14 @@ def test_demod_chunk_sizes(emu):
 
 def test_reed_solomon_random_error_patterns(emu):
     P.check_rs_random(emu, n_sf=120)
+
+
+@pytest.mark.parametrize("s", sorted(P.RS_GEOMETRIES))
+def test_reed_solomon_random_error_patterns_odd_geometries(emu, s):
+    """one code word per superframe to 48: thread -> (superframe, column) with s that divides no work-group"""
+    P.check_rs_random(emu, n_sf=P.RS_GEOMETRIES[s], seed=77 + s, s_per_sf=s)
+
+
+@pytest.mark.parametrize("s", [1, 9, 48])
+def test_reed_solomon_directed_words(emu, s):
+    P.check_rs_directed(emu, s)

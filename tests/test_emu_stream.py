@@ -76,6 +76,22 @@ def test_superframe_filter_other_bit_rates(emu):
     P.check_superframes_vs_oracle(factory, nf=20, B=1, ensemble=ens, pick=(0, 1, 2, 3), auto_modes=(True,))
 
 
+@pytest.mark.parametrize("F", [3, 5])
+def test_superframe_layouts_and_odd_bit_rates(emu, F):
+    """the four access-unit layouts, every rejection rule of CheckSync, access units of two bytes and of one, at 8 / 24 / 72 kbit/s (one,
+    three and nine code words per superframe); F = 3: superframes straddle the batches, F = 5: the wide pass takes full windows.  (The
+    device twin and DABPHY_FULL_CPU_SUITE=1 run the whole ensemble up to 384 kbit/s.)"""
+    import os
+    if os.environ.get("DABPHY_FULL_CPU_SUITE"):
+        P.check_superframe_layouts(factory, F=F, auto_modes=(True,))
+    else:
+        P.check_superframe_layouts(factory, F=F, rates=(8, 24, 72), auto_modes=(True,))
+
+
+def test_rs_decode_msc(emu):
+    P.check_rs_decode_msc(factory)
+
+
 @pytest.mark.parametrize("F,nf", [(4, 11), (1, 7), (3, 10)])
 def test_mixed_protection_classes(emu, F, nf):
     """4 / 1 / 3 frames per call = 16 / 4 / 12 CIFs per sub-channel: a wave's 64 code words span up to 5 / 17 / 7 (ensemble,

@@ -123,3 +123,14 @@ def test_timing_driver_refuses_a_stale_launch(gpu):
 
 def test_reed_solomon_random_error_patterns(gpu):
     P.check_rs_random(gpu, n_sf=600)
+
+
+@pytest.mark.parametrize("s", sorted(P.RS_GEOMETRIES))
+def test_reed_solomon_random_error_patterns_odd_geometries(gpu, s):
+    """one code word per superframe to 48: thread -> (superframe, column) with s that divides no work-group"""
+    P.check_rs_random(gpu, n_sf=P.RS_GEOMETRIES[s], seed=77 + s, s_per_sf=s)
+
+
+@pytest.mark.parametrize("s", sorted(P.RS_GEOMETRIES))
+def test_reed_solomon_directed_words(gpu, s):
+    P.check_rs_directed(gpu, s)

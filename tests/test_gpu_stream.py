@@ -89,6 +89,20 @@ def test_superframe_filter_where_the_damage_falls(gpu, F, damage_q):
     P.check_superframes_vs_oracle(factory, F=F, nf=22, B=1, damage_q=damage_q, auto_modes=(True,))
 
 
+@pytest.mark.parametrize("F", [3, 5])
+def test_superframe_layouts_and_odd_bit_rates(gpu, F):
+    """the four access-unit layouts, every rejection rule of CheckSync, access units of two bytes and of one, in one ensemble of 8 / 24 /
+    40 / 72 / 136 / 384 kbit/s (1 .. 48 code words per superframe, all three LDS buckets); F = 3: superframes straddle the batches, F = 5:
+    the wide pass takes full windows"""
+    P.check_superframe_layouts(factory, F=F)
+
+
+@pytest.mark.parametrize("F", [3, 5])
+def test_rs_decode_msc(gpu, F):
+    """(batch depths at which the de-interleaver's 16-CIF fill ends INSIDE a batch: first_valid = 4 of 12 rows, 16 of 20)"""
+    P.check_rs_decode_msc(factory, F=F)
+
+
 def test_superframe_filter_other_bit_rates(gpu):
     """the filter's other instances: 128 / 192 / 256 kbit/s (superframes of 1920 / 2880 / 3840 bytes: 16 - 32 code words, rows of more than
     one LDS-DMA request) and 32 kbit/s (4 code words: half a syndrome round), damaged superframes included, both ways through a batch"""

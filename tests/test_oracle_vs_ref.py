@@ -6,6 +6,7 @@ import pytest
 
 import parity_cases as P
 import refapi as R
+import sf_cases as S
 from welle_io_amd import synth
 
 pytestmark = pytest.mark.skipif(not R.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
@@ -76,6 +77,93 @@ def test_rs():
         pos = rng.choice(len(e), ne, replace=False); e[pos] ^= rng.randint(1, 256, ne).astype(np.uint8)
         a = R.ref_rs_superframe(e); b = R.orc_rs_superframe(e)
         assert np.array_equal(a[0], b[0]) and a[1:] == b[1:]
+
+
+@pytest.fixture(scope="module")
+def directed():
+    return S.directed_sets()
+
+
+@pytest.mark.parametrize("s", [1, 3, 8, 9, 17, 48])
+def test_rs_directed_sets(directed, s):
+    """decode_rs_char through RSDecoder::DecodeSuperframe on the directed words of tests/sf_cases.py, code word i in column i of
+    superframes of s columns: bytes, count and verdict equal the oracle's; and, judged by the reference's own output, the constructions
+    did what they claim -- roots in the padding are counted and nothing is written, a weight-11 code word with 11 - j of its bytes
+    inside the word is completed by writing the other j"""
+    rng = np.random.RandomState(100 + s)
+    for name, (rx, tx) in directed.items():
+        sfs = S.pack_columns(rx, s, rng)
+        for k, sf in enumerate(list(sfs) + [S.mixed_superframe(directed, name, s, rng)]):
+            a = R.ref_rs_superframe(sf); b = R.orc_rs_superframe(sf)
+            assert np.array_equal(a[0], b[0]) and a[1:] == b[1:], (name, s, k, a[1:], b[1:])
+    for name, (rx, tx) in directed.items():
+        kind, _, arg = name.partition(":")
+        for r, c in zip(rx, tx):
+            sf = np.zeros(120 * s, np.uint8)
+            sf[(s - 1)::s] = r                                          # alone in the last column, zero words beside it
+            out, cnt, unc = R.ref_rs_superframe(sf)
+            got = out[(s - 1)::s]
+            assert not out.reshape(120, s)[:, :s - 1].any()
+            if kind == "pad_roots":
+                assert (cnt, unc) == (int(arg), 0) and np.array_equal(got, r), (name, cnt, unc)
+            elif kind == "applied":
+                assert (cnt, unc) == (int(arg), 0) and int((got != r).sum()) == int(arg) and not np.array_equal(got, c), (name, cnt, unc)
+                assert not any(S.syndromes(got))                       # ... into another code word
+            elif kind in ("edge", "zero"):
+                w = int((r != c).sum())
+                if w <= 5:
+                    assert (cnt, unc) == (w, 0) and np.array_equal(got, c), (name, w, cnt, unc)
+
+
+def test_rs_two_errors_with_zero_s0():
+    """S0 = 0 is no special case: two errors of equal value are two corrections, in the reference and in the oracle"""
+    rng = np.random.RandomState(2)
+    for pos in ((0, 119), (109, 110), (5, 60), (118, 119)):
+        c = S.random_codeword(rng); r = c.copy(); r[list(pos)] ^= 0x5C
+        assert S.syndromes(r)[0] == 0
+        for f in (R.ref_rs_superframe, R.orc_rs_superframe):
+            out, cnt, unc = f(r)
+            assert (cnt, unc) == (2, 0) and np.array_equal(out, c)
+
+
+SF_RATES = (8, 24, 40, 72, 136, 384)
+
+
+@pytest.mark.parametrize("bitrate", SF_RATES)
+def test_superframe_layouts_equal_reference(oracle_built, bitrate):
+    """SuperframeFilter::Feed / CheckSync over the four access-unit layouts (2 / 3 / 4 / 6 units, first start 5 / 6 / 8 / 11), every way
+    CheckSync rejects a superframe with a valid Fire code or without one, access units that are nothing but their CRC, and the odd
+    geometries from one code word per superframe to 48 (audio decoding is off in the harness: no layout reaches an AAC decoder)"""
+    rng = np.random.RandomState(bitrate)
+    s = bitrate // 8
+    sfs, want_sync, n_aus = [], [], []
+    for lay, (num_aus, a0) in S.LAYOUTS.items():
+        rejects = ["zero_table", "fire", "all_zero"] + ["order:%d" % k for k in range(1, num_aus)] + (["past_end"] if 110 * s <= 4095 else [])
+        plain = [None, [2] + [None] * (num_aus - 1), [None] * (num_aus - 1) + [2], None]
+        for i, rej in enumerate(rejects):
+            sfs.append(S.make_superframe(bitrate, rng, lay, flags=int(rng.randint(0, 32)), au_lengths=plain[i % 4])); want_sync.append(1); n_aus.append(num_aus)
+            sfs.append(S.make_superframe(bitrate, rng, lay, flags=int(rng.randint(0, 32)), reject=rej)); want_sync.append(0); n_aus.append(num_aus)
+        sfs.append(S.make_superframe(bitrate, rng, lay, au_lengths=[2] * (num_aus - 1) + [None])); want_sync.append(1); n_aus.append(num_aus)
+    S.apply_damage(sfs[0], s, "within"); S.apply_damage(sfs[4], s, "beyond")
+    fb = 3 * bitrate
+    stream = np.concatenate(sfs).reshape(-1, fb)[2:]                          # start 2 frames into a superframe
+    eo, so = R.orc_superframe_run(stream)
+    er, sr = R.ref_superframe_run(stream)
+    assert eo == er
+    assert len(so) == len(sr) and all(np.array_equal(x, y) for x, y in zip(so, sr))
+    # what the reference made of the aligned attempts: superframe q (q >= 1) is complete with frame 5 q + 2
+    at = {e[0]: e for e in er}
+    for q in range(1, len(sfs)):
+        e = at.get(5 * q + 2)
+        assert e is not None, q
+        if q == 4:                                                             # (beyond repair: whatever the decoder makes of it)
+            continue
+        assert e[3] == want_sync[q], (q, e)
+        if e[3]:
+            assert e[5] == n_aus[q] and e[6][0] == S.LAYOUTS[[k for k, v in S.LAYOUTS.items() if v[0] == n_aus[q]][0]][1] and e[6][-1] == 110 * s
+    synced = [e for e in er if e[3]]
+    assert {e[5] for e in synced} == {2, 3, 4, 6}
+    assert any(e[6][i + 1] - e[6][i] == 2 and e[7] >> i & 1 for e in synced for i in range(e[5]))      # a CRC over nothing passed
 
 
 def test_ofdm_decoder_soft_bits():

@@ -170,9 +170,8 @@ int dabphy_get_fic_ratio(dabphy_handle* h, int32_t* ratio_percent)
     return DABPHY_OK;
 }
 
-namespace {
 // first_valid / n_rows of one (ensemble, sub-channel) pair as documented in include/dabphy.h (host arithmetic on the batch's descriptors)
-void msc_rows_info(const dabphy_handle* h, uint32_t b, dabphy_handle::PairRef w, int32_t* first_valid, int32_t* n_rows)
+extern "C" void msc_rows_info(const dabphy_handle* h, uint32_t b, dabphy_handle::PairRef w, int32_t* first_valid, int32_t* n_rows)
 {
     const uint32_t F = h->last_frames;
     const auto& cls = h->classes[w.cls];
@@ -188,6 +187,7 @@ void msc_rows_info(const dabphy_handle* h, uint32_t b, dabphy_handle::PairRef w,
         *n_rows = 4 * nv;
     }
 }
+namespace {
 // rows of one (ensemble, sub-channel) pair from its class's output [pair][4F][nbits / 8]
 int msc_rows_of(dabphy_handle* h, uint32_t b, dabphy_handle::PairRef w, uint8_t* out, int32_t* first_valid, int32_t* n_rows)
 {

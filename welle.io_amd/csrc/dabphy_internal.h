@@ -194,7 +194,7 @@ struct dabphy_handle {
     bool profiling = false;
     hipEvent_t ev_beg[ST_COUNT]{}, ev_end[ST_COUNT]{};
     bool ev_used[ST_COUNT]{};
-    DevBuf rs_first, rs_result;
+    DevBuf rs_first, rs_result, rs_rows;
     DevBuf s_hist;                          // [B][HIST_CAP] window searches since the last acquisition (sLevel replay in k_acquire)
     // TII (RadioReceiverOptions::decodeTII): constants, per-batch scratch, per-ensemble sums that live across batches
     bool tii_on = false; bool tii_ran = false;
@@ -354,6 +354,7 @@ DABPHY_INTERNAL int sp_variant_for(int nsteps);
 // decision scratch was laid out
 DABPHY_INTERNAL bool sp_two_for(const dabphy_handle* h, uint64_t n_cw);
 DABPHY_INTERNAL void launch_sp(const FusedArgs& a, bool two, int lds_variant, hipStream_t s);
+DABPHY_INTERNAL void msc_rows_info(const dabphy_handle* h, uint32_t b, dabphy_handle::PairRef w, int32_t* first_valid, int32_t* n_rows);   // dabphy_getters.hip: rows [first_valid, n_rows) of a pair's class output are the batch's logical frames
 DABPHY_INTERNAL int drain_wait(dabphy_handle* h);                                                // dabphy_getters.hip: host waits for a bulk MSC drain in flight
 DABPHY_INTERNAL size_t soft_ens_stride(const dabphy_handle* h);                                   // bytes between the soft-bit ring slices of two ensembles
 }

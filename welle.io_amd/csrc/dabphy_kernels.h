@@ -293,8 +293,8 @@ struct RsArgs {            // contiguous superframes [n_sf][sf_stride], s = bitr
 struct RsMscArgs {         // superframes inside a class's MSC output [n_pairs][n_cif][frame_bytes]
     uint8_t* out; int n_cif, n_pairs, frame_bytes, s, n_sf_per_pair;
     const MscPair* pairs;
-    int idx_only;                                 // -1: every pair, else only the pairs at this position of their ensemble's list
     const int* first_cif;                         // [B] logical-frame slot (in this batch) where the ensemble's first superframe starts
+    const int2* rows;                             // [n_pairs] rows [x, y) of the pair hold this batch's logical frames (first_valid, n_rows); x >= y: the pair is left out
     int* result;                                  // [n_pairs][n_sf_per_pair][2] = corrected symbols, uncorrectable flag
 };
 // DAB+ superframe filter (k_rs.hip: k_superframe): SuperframeFilter::Feed over the logical frames of one batch

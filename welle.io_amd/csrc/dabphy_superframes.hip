@@ -73,21 +73,33 @@ int dabphy_rs_decode_msc(dabphy_handle* h, int32_t subch_index, const int32_t* f
     HIPCHK(h, hipMemcpyAsync(h->rs_first.p, first_cif, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
     if (corrected) memset(corrected, 0, sizeof(int32_t) * B);
     if (uncorrectable) memset(uncorrectable, 0, sizeof(int32_t) * B);
-    bool first_launch = true, any = subch_index < 0;
+    // Per pair the rows that hold this batch's logical frames (dabphy_get_msc); a pair the call leaves out gets an empty range: another list
+    // position than the one asked for, or an MP2 service -- its bytes are no Reed-Solomon code words (dabphy_set_audio_kinds_ensemble)
+    bool first_launch = true, any = subch_index < 0, any_at_index = false;
+    std::vector<std::vector<int2>> rows_of(h->classes.size());       // (host sources of queued copies: they live until the stream has been synchronised)
     for (auto& cls : h->classes) {
-        if (subch_index >= 0) {
-            bool here = false;
-            for (const MscPair& p : cls.pairs) if (p.idx == subch_index) { here = true; break; }
-            if (!here) continue;
-            any = true;
-        }
         const int bitrate = cls.prot.nbits / 24;
-        if (bitrate % 8) continue;
         const size_t P = cls.pairs.size(), nres = P * n_sf * 2;
+        std::vector<int2>& rows = rows_of[&cls - h->classes.data()];
+        rows.assign(P, make_int2(0, 0));
+        bool work = false;
+        for (size_t p = 0; p < P; p++) {
+            const MscPair& pp = cls.pairs[p];
+            if (subch_index >= 0 && pp.idx != subch_index) continue;
+            any_at_index = true;
+            if (cls.kind[p] == DABPHY_AUDIO_MP2) continue;
+            any = true;
+            dabphy_handle::PairRef w; w.cls = (int)(&cls - h->classes.data()); w.pair = (int)p;
+            msc_rows_info(h, (uint32_t)pp.ens, w, &rows[p].x, &rows[p].y);
+            work |= rows[p].x < rows[p].y;
+        }
+        if (bitrate % 8 || !work) continue;
         if ((r = ensure(h, h->rs_result, nres * sizeof(int)))) return r;
+        if ((r = ensure(h, h->rs_rows, P * sizeof(int2)))) return r;
         HIPCHK(h, hipMemsetAsync(h->rs_result.p, 0, nres * sizeof(int), h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->rs_rows.p, rows.data(), P * sizeof(int2), hipMemcpyHostToDevice, h->stream));
         RsMscArgs a{}; a.out = cls.out.as<uint8_t>(); a.n_cif = n_cif; a.n_pairs = (int)P; a.pairs = cls.pair_tab.as<MscPair>();
-        a.frame_bytes = cls.prot.nbits / 8; a.s = bitrate / 8; a.n_sf_per_pair = n_sf; a.idx_only = subch_index;
+        a.frame_bytes = cls.prot.nbits / 8; a.s = bitrate / 8; a.n_sf_per_pair = n_sf; a.rows = h->rs_rows.as<int2>();
         a.first_cif = h->rs_first.as<int>(); a.result = h->rs_result.as<int>();
         if (h->profiling && first_launch) { hipError_t e = hipEventRecord(h->ev_beg[dabphy_handle::ST_RS], h->stream); (void)e; }
         launch_rs_msc(a, h->stream);
@@ -105,7 +117,11 @@ int dabphy_rs_decode_msc(dabphy_handle* h, int32_t subch_index, const int32_t* f
                 }
         }
     }
-    if (!any) return DABPHY_ERR_INVALID;                             // no ensemble has a sub-channel at that position
+    if (!any) {                                                      // no ensemble has a sub-channel at that position, or only MP2 services
+        h->err = any_at_index ? "the sub-channel at this position is an MP2 service in every ensemble that has one" : "no ensemble has a sub-channel at this position";
+        r = sync(h);
+        return r ? r : DABPHY_ERR_INVALID;
+    }
     return sync(h);
 }
 

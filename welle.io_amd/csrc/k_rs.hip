@@ -9,8 +9,12 @@
 // bytes sf[pos*s + i], pos = 0..119.  Consecutive threads take consecutive i, so every syndrome step reads s
 // consecutive bytes.  Syndromes -> locator (Massey) -> roots -> values, register-resident (rs_correct120); corrected
 // bytes, the corrected-symbol count and the "uncorrectable" verdict equal the reference's also for words beyond the
-// correction capacity (miscorrections included: tests/golden rs vectors, random error patterns of weight 0 .. 12 against
-// the oracle, which is pinned to decode_rs_char itself).  GF tables live in LDS.
+// correction capacity (miscorrections included).  What pins it, each against the oracle, which is pinned to decode_rs_char itself
+// (tests/test_oracle_vs_ref.py): tests/golden rs vectors; random error patterns of weight 0 .. 12 at 1 .. 48 code words per superframe
+// (check_rs_random); words built for the corner paths -- roots in the padding, miscorrections written in full, errors at the edges of
+// the shortened code, zero data, S0 = 0 (check_rs_directed, tests/sf_cases.py); k_rs_msc by value on the class outputs of a stream
+// (check_rs_decode_msc); the filter over the four access-unit layouts, every rejection rule and 8 .. 384 kbit/s
+// (check_superframe_layouts).  GF tables live in LDS.
 //
 // Second half of the file: the DAB+ superframe filter (SuperframeFilter::Feed / CheckSync, dabplus_decoder.cpp:50-213) on the
 // class output of a batch -- k_superframe_wide + k_superframe_settle (every attempt a receiver in lock makes in the batch at once,
@@ -222,9 +226,10 @@ __global__ void __launch_bounds__(256) k_rs_msc(RsMscArgs A)
     const int pair = idx / per_pair; const int rem = idx % per_pair;
     const int q = rem / A.s, i = rem % A.s;
     const MscPair pp = A.pairs[pair];
-    if (A.idx_only >= 0 && pp.idx != A.idx_only) return;
-    const int r0 = A.first_cif[pp.ens] + 5 * q;                  // first logical frame of superframe q
-    if (r0 < 0 || r0 + 5 > A.n_cif) return;
+    const int2 rows = A.rows[pair];
+    const int fc = A.first_cif[pp.ens];
+    const int r0 = fc + 5 * (q + (fc < 0 ? -fc / 5 : 0));        // first logical frame of superframe q (of those that do not end in front of row 0, however far back the alignment was given)
+    if (r0 < rows.x || r0 + 5 > rows.y) return;                  // a superframe that touches a row outside the batch's frames is neither decoded nor counted
     RsMscIo io;
     io.frame_bytes = A.frame_bytes; io.s = A.s; io.i = i; io.frame_stride = (size_t)A.frame_bytes;
     io.frames = A.out + ((size_t)pair * A.n_cif + r0) * A.frame_bytes;
