@@ -32,7 +32,7 @@ extern hipemu_idx threadIdx, blockIdx, blockDim, gridDim;
 
 typedef int hipError_t;
 typedef void* hipStream_t;
-typedef struct hipemu_event { std::chrono::steady_clock::time_point t; }* hipEvent_t;
+typedef struct hipemu_event { std::chrono::steady_clock::time_point t; int64_t id; }* hipEvent_t;
 enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorNoDevice = 100 };
 enum hipMemcpyKind { hipMemcpyHostToHost, hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice, hipMemcpyDefault };
 struct hipDeviceProp_t { char name[256]; char gcnArchName[256]; int multiProcessorCount; size_t totalGlobalMem; };
@@ -60,22 +60,31 @@ hipError_t hipEventDestroy(hipEvent_t e);
 // library was loaded, in order, as (flags, priority) pairs (returns how many there are, writes at most `cap` of them)
 extern "C" void hipemu_live_counts(int64_t out[4]);
 extern "C" int64_t hipemu_stream_creations(int64_t* flags_priority, int64_t cap);
+// Queue-order trace: what is handed to which stream in which order -- the one thing a model that runs everything at once cannot
+// otherwise show.  hipemu_trace_start clears the records and switches recording on; streams and events are then named by the order
+// in which they are created from that call on (so: call it in front of dabphy_create), "-" is the null stream, older ones print "?".
+// hipemu_trace_read copies at most `cap` bytes of the text so far (one line per record: op stream event kernel grid block bytes)
+// and returns its whole length.  Every traced call below goes through the one hook hipemu_trace_op.
+extern "C" void hipemu_trace_start();
+extern "C" int64_t hipemu_trace_read(char* text, int64_t cap);
+void hipemu_trace_op(const char* op, hipStream_t s, hipEvent_t e = nullptr, const char* kernel = nullptr, dim3 grid = dim3(0), dim3 block = dim3(0), size_t bytes = 0);
 static inline hipError_t hipHostGetDevicePointer(void** dp, void* hp, unsigned = 0) { *dp = hp; return hipSuccess; }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memmove(d, s, n); return hipSuccess; }
-static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t = nullptr) { memmove(d, s, n); return hipSuccess; }
-static inline hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t = nullptr)
+static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t st = nullptr) { hipemu_trace_op("memcpy", st, nullptr, nullptr, dim3(0), dim3(0), n); memmove(d, s, n); return hipSuccess; }
+static inline hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t st = nullptr)
 {
+    hipemu_trace_op("memcpy2d", st, nullptr, nullptr, dim3(0), dim3(0), width * height);
     for (size_t r = 0; r < height; r++) memmove((char*)d + r * dpitch, (const char*)s + r * spitch, width);
     return hipSuccess;
 }
 static inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
-static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t = nullptr) { memset(d, v, n); return hipSuccess; }
+static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st = nullptr) { hipemu_trace_op("memset", st, nullptr, nullptr, dim3(0), dim3(0), n); memset(d, v, n); return hipSuccess; }
 static inline hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 0; *hi = -1; return hipSuccess; }      // (least, greatest: numerically lower = higher, as on the device)
-static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+static inline hipError_t hipStreamSynchronize(hipStream_t st) { hipemu_trace_op("stream_sync", st); return hipSuccess; }
 static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
-static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t = nullptr) { e->t = std::chrono::steady_clock::now(); return hipSuccess; }
-static inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
+static inline hipError_t hipStreamWaitEvent(hipStream_t st, hipEvent_t e, unsigned) { hipemu_trace_op("wait", st, e); return hipSuccess; }
+static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t st = nullptr) { hipemu_trace_op("record", st, e); e->t = std::chrono::steady_clock::now(); return hipSuccess; }
+static inline hipError_t hipEventSynchronize(hipEvent_t e) { hipemu_trace_op("event_sync", nullptr, e); return hipSuccess; }
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) { *ms = std::chrono::duration<float, std::milli>(b->t - a->t).count(); return hipSuccess; }
 static inline hipError_t hipPointerGetAttributes(void*, const void*) { return hipErrorInvalidValue; }
 #define hipStreamNonBlocking 1
@@ -101,7 +110,7 @@ static inline unsigned long long hipemu_ballot(bool p)
 }
 
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-    hipemu_launch(dim3(grid), dim3(block), [=]() { kernel(__VA_ARGS__); })
+    (hipemu_trace_op("launch", stream, nullptr, #kernel, dim3(grid), dim3(block)), hipemu_launch(dim3(grid), dim3(block), [=]() { kernel(__VA_ARGS__); }))
 
 static inline void __syncthreads() { asm volatile("" ::: "memory"); hipemu_syncthreads(); asm volatile("" ::: "memory"); }
 static inline int hipemu_lane() { return (int)((threadIdx.x + threadIdx.y * blockDim.x) & 63); }

@@ -3,6 +3,8 @@
 #include <stdexcept>
 #include <mutex>
 #include <set>
+#include <algorithm>
+#include <string>
 #include <utility>
 
 hipemu_idx threadIdx, blockIdx, blockDim, gridDim;
@@ -136,7 +138,10 @@ const char* const live_name[LIVE_KINDS] = {"hipFree", "hipHostFree", "hipStreamD
 std::mutex g_live_mutex;
 std::set<const void*> g_live[LIVE_KINDS];
 std::vector<std::pair<int64_t, int64_t>> g_stream_log;
-struct StreamObj { unsigned flags; int priority; };
+struct StreamObj { unsigned flags; int priority; int64_t id; };
+int64_t g_events_created = 0;
+// queue-order trace (hip_runtime.h): the text so far, and the creation counts at hipemu_trace_start that stream / event names count from
+bool g_trace_on = false; std::string g_trace; int64_t g_trace_stream0 = 0, g_trace_event0 = 0;
 
 void born(int kind, const void* p) { std::lock_guard<std::mutex> l(g_live_mutex); g_live[kind].insert(p); }
 void gone(int kind, const void* p)
@@ -155,9 +160,9 @@ hipError_t new_block(int kind, void** p, size_t n)
 }
 hipError_t new_stream(hipStream_t* s, unsigned flags, int priority)
 {
-    *s = new StreamObj{flags, priority};
-    born(LIVE_STREAM, *s);
     std::lock_guard<std::mutex> l(g_live_mutex);
+    *s = new StreamObj{flags, priority, (int64_t)g_stream_log.size()};
+    g_live[LIVE_STREAM].insert(*s);
     g_stream_log.emplace_back((int64_t)flags, (int64_t)priority);
     return hipSuccess;
 }
@@ -171,7 +176,13 @@ hipError_t hipStreamCreate(hipStream_t* s) { return new_stream(s, 0, 0); }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned flags) { return new_stream(s, flags, 0); }
 hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned flags, int priority) { return new_stream(s, flags, priority); }
 hipError_t hipStreamDestroy(hipStream_t s) { gone(LIVE_STREAM, s); delete static_cast<StreamObj*>(s); return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t* e) { *e = new hipemu_event; born(LIVE_EVENT, *e); return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t* e)
+{
+    std::lock_guard<std::mutex> l(g_live_mutex);
+    *e = new hipemu_event{{}, g_events_created++};
+    g_live[LIVE_EVENT].insert(*e);
+    return hipSuccess;
+}
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
 hipError_t hipEventDestroy(hipEvent_t e) { gone(LIVE_EVENT, e); delete e; return hipSuccess; }
 
@@ -185,4 +196,26 @@ extern "C" int64_t hipemu_stream_creations(int64_t* flags_priority, int64_t cap)
     std::lock_guard<std::mutex> l(g_live_mutex);
     for (int64_t i = 0; i < cap && i < (int64_t)g_stream_log.size(); i++) { flags_priority[2 * i] = g_stream_log[i].first; flags_priority[2 * i + 1] = g_stream_log[i].second; }
     return (int64_t)g_stream_log.size();
+}
+
+extern "C" void hipemu_trace_start()
+{
+    std::lock_guard<std::mutex> l(g_live_mutex);
+    g_trace_on = true; g_trace.clear(); g_trace_stream0 = (int64_t)g_stream_log.size(); g_trace_event0 = g_events_created;
+}
+extern "C" int64_t hipemu_trace_read(char* text, int64_t cap)
+{
+    std::lock_guard<std::mutex> l(g_live_mutex);
+    if (text && cap > 0) memcpy(text, g_trace.data(), std::min<size_t>((size_t)cap, g_trace.size()));
+    return (int64_t)g_trace.size();
+}
+void hipemu_trace_op(const char* op, hipStream_t s, hipEvent_t e, const char* kernel, dim3 grid, dim3 block, size_t bytes)
+{
+    if (!g_trace_on) return;
+    std::lock_guard<std::mutex> l(g_live_mutex);
+    auto name = [](char c, bool null, int64_t id) { return null ? std::string("-") : id < 0 ? std::string(1, c) + "?" : c + std::to_string(id); };
+    char dims[96] = "- -";
+    if (kernel) snprintf(dims, sizeof dims, "%ux%ux%u %ux%ux%u", grid.x, grid.y, grid.z, block.x, block.y, block.z);
+    g_trace += std::string(op) + " " + name('s', !s, s ? static_cast<StreamObj*>(s)->id - g_trace_stream0 : 0) + " " + name('e', !e, e ? e->id - g_trace_event0 : 0) + " "
+             + (kernel ? kernel : "-") + " " + dims + " " + (bytes ? std::to_string(bytes) : std::string("-")) + "\n";
 }

@@ -2,7 +2,7 @@
 // receiver batch), small host helpers, and the internal functions that cross files.  Not installed, not part of include/dabphy.h.
 //   dabphy_api.hip          create / destroy / options / sub-channel classes, the stateless seams (demod, Viterbi, FIC, RS) and the timing drivers
 //   dabphy_stream.hip       sample rings (bind / upload / write / raw formats), the synchroniser's chain and wide pass, reset
-//   dabphy_process.hip      dabphy_process: the pipelined schedules, exact batch mode (replay), the decode of one batch
+//   dabphy_process.hip      dabphy_process: the pipelined schedules, exact batch mode (replay), the decode of one batch as named steps
 //   dabphy_fused.hip        the fused decode's host side: per-class step tables, the launch plan (build, classes, work list)
 //   dabphy_superframes.hip  Reed-Solomon seams and the DAB+ superframe filter
 //   dabphy_mp2.hip          classic DAB (MP2) services: audio kinds, the MP2 frame check and its unit entry
@@ -58,6 +58,8 @@ struct SfSel { int cls; const int32_t* d_run; int n_run; };
 constexpr int SP_SINGLE_MAX_GROUPS = 4096;   // groups of 64 code words a one-class state-parallel launch takes (sp_single_*: the seams, the replay's FIC)
 constexpr int SF_BATCH_CLASSES = 256;                                                        // classes per bucket (a handle has at most 255)
 constexpr size_t SF_BATCH_BYTES = 3 * (SF_BATCH_CLASSES * sizeof(SfArgs) + (SF_BATCH_CLASSES + 1) * sizeof(int32_t) + 12);
+// DABPHY_DEBUG_TIMING=1: host-side time line of dabphy_process (microseconds since entry, averaged, printed every 8th call)
+struct HostTimeline { double acc[6] = {0, 0, 0, 0, 0, 0}; long n = 0; };
 } // namespace dabphy
 using namespace dabphy;          // (internal header: the handle below names the kernels' argument blocks)
 
@@ -184,6 +186,7 @@ struct dabphy_handle {
     uint32_t presynced = 0;           // frames already synchronised ahead into s_desc2[desc_sel] (pipelined mode)
     int soft_ring = 0;
     uint32_t last_frames = 0;         // n_frames of the last dabphy_process
+    HostTimeline tl; int tl_on = -1;  // (experiments builds: read through debug_env on the first call)
     float* cur_cir = nullptr;
     FrameDesc* h_desc = nullptr;      // host copy of the last batch's frame descriptors (page-locked, [B][max_frames])
     float* h_snr = nullptr;
@@ -301,6 +304,35 @@ struct ScopedEvent {
 // (ofdm-processor.cpp:397-409: the ratio of the PREVIOUS frame): batches of several frames, and ONE frame per call too when the
 // synchroniser runs ahead of the decoder (pipeline_sync 1-3).  One frame per call on the serial schedule is exact by construction.
 inline bool replay_armed(const dabphy_handle* h, uint32_t F) { return h->exact_batch && (F > 1 || h->cfg.pipeline_sync != 0); }
+
+// What a batch carries over from the one before it -- THE list: exact batch mode reserves a snapshot for every entry, saves it in
+// front of the first pass and puts it back in front of the second (dabphy_process.hip), dabphy_reset zeroes the live blocks
+// (every = true: whatever exists, whether or not the current options would snapshot it).  fn(live block, its snapshot, bytes);
+// the first non-zero return ends the walk.  Copies skip an entry whose block or snapshot does not exist (copy_carried).
+// The decoders' share: decoder state, TII sums, superframe windows and MP2 parser state per class ...
+template <typename Fn> int for_each_carried(dabphy_handle* h, bool every, Fn fn)
+{
+    int r;
+    if ((r = fn((void*)h->d_dec, h->snap_dec, sizeof(DecState) * h->cfg.n_ensembles))) return r;
+    if ((r = fn(h->tii_state.p, h->snap_tii, h->tii_state.cap))) return r;
+    // (deferred filter: this batch's pass has not run when the batch is decoded again, nothing to put back)
+    if (every || !h->sf_deferred) for (auto& cls : h->classes) if ((r = fn(cls.sf_state.p, cls.sf_snap, cls.sf_state.cap))) return r;
+    if (every || h->mp2_auto) for (auto& cls : h->classes) if ((every || cls.n_mp2) && (r = fn(cls.mp2_state.p, cls.mp2_snap, cls.mp2_state.cap))) return r;
+    return 0;
+}
+// ... and the synchroniser's, per descriptor buffer: its state and the history ring that state indexes.  Saved on the synchroniser's
+// stream when the buffer's chain is queued (queue_chain), put back on the main stream with the rest.
+template <typename Fn> int for_each_carried_sync(dabphy_handle* h, int sel, Fn fn)
+{
+    int r;
+    if ((r = fn((void*)h->d_state, h->snap_state[sel], sizeof(RxState) * h->cfg.n_ensembles))) return r;
+    return fn(h->s_hist.p, h->snap_hist[sel], (size_t)h->cfg.n_ensembles * HIST_CAP * sizeof(FrameDesc));
+}
+inline int copy_carried(dabphy_handle* h, void* dst, const void* src, size_t bytes, hipStream_t st)
+{
+    if (dst && src) HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
 
 inline int sync(dabphy_handle* h)
 {

@@ -74,7 +74,6 @@ int prepare_mp2(dabphy_handle* h, uint32_t F)
         if ((r = ensure(h, c.mp2_n, P * sizeof(int32_t)))) return r;
         if ((r = ensure(h, c.mp2_err, P * n_cif * sizeof(int32_t)))) return r;
         if ((r = ensure(h, c.mp2_fu, P * sizeof(int32_t)))) return r;
-        if (h->exact_batch && (r = ensure(h, c.mp2_snap, c.mp2_state.cap))) return r;
     }
     if (any && (r = ensure(h, h->mp2_stats, sizeof(int32_t) * 4 * h->cfg.n_ensembles))) return r;
     return DABPHY_OK;

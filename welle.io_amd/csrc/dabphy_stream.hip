@@ -42,13 +42,13 @@ int queue_chain(dabphy_handle* h, int sel, uint32_t F)
 {
     SyncArgs sa = sync_args(h, sel, F, h->s_valid);
     h->chain_valid[sel] = h->s_valid; h->chain_frames[sel] = F;
-    if (replay_armed(h, F) && h->snap_state[sel].p)              // (one frame per call on the serial schedule is exact by construction: nothing to put back)
-    {
-        HIPCHK(h, hipMemcpyAsync(h->snap_state[sel].p, h->d_state, sizeof(RxState) * h->cfg.n_ensembles, hipMemcpyDeviceToDevice, h->sync_stream));
-        // ... and the history ring its hist_head / hist_count index: an acquisition inside the batch restarts the ring at entry 0, over the
-        // window searches the second pass has to replay through the sLevel recurrence when it loses lock at the same frame
-        if (h->snap_hist[sel].p && h->s_hist.p)
-            HIPCHK(h, hipMemcpyAsync(h->snap_hist[sel].p, h->s_hist.p, (size_t)h->cfg.n_ensembles * HIST_CAP * sizeof(FrameDesc), hipMemcpyDeviceToDevice, h->sync_stream));
+    // the synchroniser's share of what exact batch mode puts back (one frame per call on the serial schedule is exact by construction:
+    // nothing to save).  The history ring goes with the state whose hist_head / hist_count index it: an acquisition inside the batch
+    // restarts the ring at entry 0, over the window searches the second pass has to replay through the sLevel recurrence when it
+    // loses lock at the same frame
+    if (replay_armed(h, F) && h->snap_state[sel].p) {
+        const int rc = for_each_carried_sync(h, sel, [&](void* live, DevBuf& snap, size_t bytes) { return copy_carried(h, snap.p, live, bytes, h->sync_stream); });
+        if (rc) return rc;
     }
     { hipError_t e = hipEventRecord(h->ev_chain_beg[sel], h->sync_stream); (void)e; }
     // one frame per call (the real-time facade) gains nothing from the wide pass; two batches ahead its verdict would come too late
@@ -133,16 +133,16 @@ int dabphy_reset(dabphy_handle* h)
     if (!h) return DABPHY_ERR_INVALID;
     int r = reset_synchroniser(h, true); if (r) return r;
     h->desc_sel = 0; h->n_wide_passes = h->n_wide_fallbacks = 0; h->n_replayed_batches = 0;
-    HIPCHK(h, hipMemsetAsync(h->d_dec, 0, sizeof(DecState) * h->cfg.n_ensembles, h->stream));
     h->last_frames = 0; h->last_desc = nullptr;
     if (h->rs_stream) HIPCHK(h, hipStreamSynchronize(h->rs_stream));
     h->sf_def_pending = h->sf_def_unfetched = h->sf_def_inflight = false;      // (a deferred filter pass of the stream that ends here is dropped with it)
-    for (auto& c : h->classes) if (c.sf_state.p) HIPCHK(h, hipMemsetAsync(c.sf_state.p, 0, c.sf_state.cap, h->stream));   // decoders restart too (RadioReceiver::restart_decoder)
-    for (auto& c : h->classes) if (c.mp2_state.p) HIPCHK(h, hipMemsetAsync(c.mp2_state.p, 0, c.mp2_state.cap, h->stream));   // (MP2 parsers too)
+    // everything the decoders carry from batch to batch starts from zero (RadioReceiver::restart_decoder; a new OFDMProcessor owns a new
+    // TIIDecoder); the pair tables and their cif0 below are reset too but are no snapshot of exact batch mode, so they stand apart
+    r = for_each_carried(h, true, [&](void* live, DevBuf&, size_t bytes) -> int { if (live) HIPCHK(h, hipMemsetAsync(live, 0, bytes, h->stream)); return 0; });
+    if (r) return r;
     h->mp2_done = false;
     // ... and the frame count starts over: every selected sub-channel's time de-interleaver fills again from the first CIF decoded
     for (auto& c : h->classes) { for (MscPair& p : c.pairs) p.cif0 = -1; int r2 = upload_pairs(h, c); if (r2) return r2; }
-    if (h->tii_state.p) HIPCHK(h, hipMemsetAsync(h->tii_state.p, 0, h->tii_state.cap, h->stream));      // a new OFDMProcessor owns a new TIIDecoder
     h->tii_ran = false;
     return sync(h);
 }
