@@ -435,10 +435,12 @@ int dabphy_superframes_stats(dabphy_handle* h, int32_t* stats);
  * submission (no host round trip between decode and filter); dabphy_superframes_stats then only fetches the totals of the batch.
  * on = 2: the pass of a batch is DEFERRED to the next dabphy_process, which queues it beside its own FFT stage on a stream of its own
  * (nothing of the next batch needs the filter's results before its decoders overwrite the class outputs, and those wait for the pass
- * on the device): the filter leaves the step's tail.  dabphy_superframes_stats then returns the totals of the batch BEFORE the last
- * dabphy_process (zeros after the first one); one more call without a dabphy_process in between runs the last batch's pass at once and
- * returns its totals (the end of a stream).  Every batch is filtered exactly once either way, with the same results.  A change of
- * the sub-channel lists, dabphy_reset and switching the mode run or drop what is pending first.
+ * on the device): the filter leaves the step's tail.  The first dabphy_superframes_stats after a dabphy_process then returns the totals
+ * of the batch BEFORE that dabphy_process (zeros after the first one); one more call without a dabphy_process in between runs the last
+ * batch's pass at once and returns its totals (the end of a stream); with nothing pending it returns zeros.  Every batch is filtered
+ * exactly once either way, with the same results.  What is pending is RUN first, and waited for, by a change of the sub-channel lists
+ * or audio kinds, by a dabphy_process with another n_frames than the last, and by leaving the mode (the next dabphy_superframes_stats
+ * then returns that batch's totals, the new mode does not filter it again); dabphy_reset DROPS it with the stream.
  * on = 0: dabphy_superframes_stats runs the pass when it is called. */
 int dabphy_set_auto_superframes(dabphy_handle* h, int32_t on);
 

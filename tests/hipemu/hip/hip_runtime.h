@@ -32,7 +32,7 @@ extern hipemu_idx threadIdx, blockIdx, blockDim, gridDim;
 
 typedef int hipError_t;
 typedef void* hipStream_t;
-typedef struct hipemu_event { std::chrono::steady_clock::time_point t; int64_t id; }* hipEvent_t;
+typedef struct hipemu_event { std::chrono::steady_clock::time_point t; int64_t id; int queued = 0; }* hipEvent_t;      // (queued: records of it that wait in a held stream)
 enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorNoDevice = 100 };
 enum hipMemcpyKind { hipMemcpyHostToHost, hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice, hipMemcpyDefault };
 struct hipDeviceProp_t { char name[256]; char gcnArchName[256]; int multiProcessorCount; size_t totalGlobalMem; };
@@ -69,22 +69,62 @@ extern "C" void hipemu_trace_start();
 extern "C" int64_t hipemu_trace_read(char* text, int64_t cap);
 void hipemu_trace_op(const char* op, hipStream_t s, hipEvent_t e = nullptr, const char* kernel = nullptr, dim3 grid = dim3(0), dim3 block = dim3(0), size_t bytes = 0);
 static inline hipError_t hipHostGetDevicePointer(void** dp, void* hp, unsigned = 0) { *dp = hp; return hipSuccess; }
-static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memmove(d, s, n); return hipSuccess; }
-static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t st = nullptr) { hipemu_trace_op("memcpy", st, nullptr, nullptr, dim3(0), dim3(0), n); memmove(d, s, n); return hipSuccess; }
-static inline hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t st = nullptr)
+// Held stream (hipemu.cpp): the model runs every op when it is queued, which is ONE of the orders the device may choose -- the earliest.
+// hipemu_hold_stream(index) (index = creation order since hipemu_trace_start, as in the trace) gives one stream the latest legal
+// order instead: launches, asynchronous copies and fills, and event records handed to it wait in a queue and run, in order and only
+// as far as needed, when something the runtime orders behind them is met -- a synchronisation of that stream or of the device, a
+// synchronous copy or fill, a release (the device synchronises there), hipEventSynchronize or ANY stream's hipStreamWaitEvent on an
+// event whose last record is in the queue.  A missing cross-stream wait then shows: the other streams' work runs first.  A
+// host-to-device copy takes its source bytes at the call, as the runtime's staging does for pageable memory.  Limit: a kernel of an
+// eager stream that spins on a flag a kernel of the held stream publishes would wait for ever -- holding that stream is not an order
+// the device can produce, such pairs are left out by the tests.  For single-threaded programs.
+extern "C" void hipemu_hold_stream(int64_t index);
+extern "C" void hipemu_hold_none();                      // runs what is queued, holds nothing from here on
+bool hipemu_held(hipStream_t st);
+void hipemu_defer(std::function<void()> op, hipEvent_t recorded = nullptr);
+void hipemu_drain();                                     // everything queued
+void hipemu_drain_event(hipEvent_t e);                   // up to the last queued record of e
+static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { hipemu_drain(); memmove(d, s, n); return hipSuccess; }
+static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind kind, hipStream_t st = nullptr)
 {
-    hipemu_trace_op("memcpy2d", st, nullptr, nullptr, dim3(0), dim3(0), width * height);
-    for (size_t r = 0; r < height; r++) memmove((char*)d + r * dpitch, (const char*)s + r * spitch, width);
+    hipemu_trace_op("memcpy", st, nullptr, nullptr, dim3(0), dim3(0), n);
+    if (!hipemu_held(st)) { memmove(d, s, n); return hipSuccess; }
+    if (kind == hipMemcpyHostToDevice) { std::vector<char> staged((const char*)s, (const char*)s + n); hipemu_defer([d, staged]() { memcpy(d, staged.data(), staged.size()); }); }
+    else hipemu_defer([d, s, n]() { memmove(d, s, n); });
     return hipSuccess;
 }
-static inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
-static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st = nullptr) { hipemu_trace_op("memset", st, nullptr, nullptr, dim3(0), dim3(0), n); memset(d, v, n); return hipSuccess; }
+static inline hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s, size_t spitch, size_t width, size_t height, hipMemcpyKind kind, hipStream_t st = nullptr)
+{
+    hipemu_trace_op("memcpy2d", st, nullptr, nullptr, dim3(0), dim3(0), width * height);
+    const auto rows = [=](const char* src, size_t pitch) { for (size_t r = 0; r < height; r++) memmove((char*)d + r * dpitch, src + r * pitch, width); };
+    if (!hipemu_held(st)) { rows((const char*)s, spitch); return hipSuccess; }
+    if (kind == hipMemcpyHostToDevice) {
+        std::vector<char> staged(width * height);
+        for (size_t r = 0; r < height; r++) memcpy(staged.data() + r * width, (const char*)s + r * spitch, width);
+        hipemu_defer([rows, staged, width]() { rows(staged.data(), width); });
+    }
+    else hipemu_defer([rows, s, spitch]() { rows((const char*)s, spitch); });
+    return hipSuccess;
+}
+static inline hipError_t hipMemset(void* d, int v, size_t n) { hipemu_drain(); memset(d, v, n); return hipSuccess; }
+static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st = nullptr)
+{
+    hipemu_trace_op("memset", st, nullptr, nullptr, dim3(0), dim3(0), n);
+    if (hipemu_held(st)) hipemu_defer([d, v, n]() { memset(d, v, n); }); else memset(d, v, n);
+    return hipSuccess;
+}
 static inline hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 0; *hi = -1; return hipSuccess; }      // (least, greatest: numerically lower = higher, as on the device)
-static inline hipError_t hipStreamSynchronize(hipStream_t st) { hipemu_trace_op("stream_sync", st); return hipSuccess; }
-static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
-static inline hipError_t hipStreamWaitEvent(hipStream_t st, hipEvent_t e, unsigned) { hipemu_trace_op("wait", st, e); return hipSuccess; }
-static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t st = nullptr) { hipemu_trace_op("record", st, e); e->t = std::chrono::steady_clock::now(); return hipSuccess; }
-static inline hipError_t hipEventSynchronize(hipEvent_t e) { hipemu_trace_op("event_sync", nullptr, e); return hipSuccess; }
+static inline hipError_t hipStreamSynchronize(hipStream_t st) { hipemu_trace_op("stream_sync", st); if (hipemu_held(st)) hipemu_drain(); return hipSuccess; }
+static inline hipError_t hipDeviceSynchronize() { hipemu_drain(); return hipSuccess; }
+// (a held stream's own wait needs nothing: what it waits for has run -- eager streams run at once -- or stands in front of it in its queue)
+static inline hipError_t hipStreamWaitEvent(hipStream_t st, hipEvent_t e, unsigned) { hipemu_trace_op("wait", st, e); if (!hipemu_held(st)) hipemu_drain_event(e); return hipSuccess; }
+static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t st = nullptr)
+{
+    hipemu_trace_op("record", st, e);
+    if (hipemu_held(st)) hipemu_defer([e]() { e->t = std::chrono::steady_clock::now(); }, e); else e->t = std::chrono::steady_clock::now();
+    return hipSuccess;
+}
+static inline hipError_t hipEventSynchronize(hipEvent_t e) { hipemu_trace_op("event_sync", nullptr, e); hipemu_drain_event(e); return hipSuccess; }
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) { *ms = std::chrono::duration<float, std::milli>(b->t - a->t).count(); return hipSuccess; }
 static inline hipError_t hipPointerGetAttributes(void*, const void*) { return hipErrorInvalidValue; }
 #define hipStreamNonBlocking 1
@@ -94,6 +134,7 @@ static inline hipError_t hipPointerGetAttributes(void*, const void*) { return hi
 
 // ---- execution engine (hipemu.cpp) ----
 void hipemu_launch(dim3 grid, dim3 block, const std::function<void()>& body);
+void hipemu_launch_on(hipStream_t st, dim3 grid, dim3 block, std::function<void()> body);     // at once, or queued when st is held (the body holds the arguments by value)
 void hipemu_syncthreads();
 unsigned hipemu_wave_exchange_impl(unsigned v, int src_lane, bool valid);   // returns v of src_lane
 unsigned long long hipemu_ballot_impl(bool p);
@@ -110,7 +151,7 @@ static inline unsigned long long hipemu_ballot(bool p)
 }
 
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-    (hipemu_trace_op("launch", stream, nullptr, #kernel, dim3(grid), dim3(block)), hipemu_launch(dim3(grid), dim3(block), [=]() { kernel(__VA_ARGS__); }))
+    (hipemu_trace_op("launch", stream, nullptr, #kernel, dim3(grid), dim3(block)), hipemu_launch_on(stream, dim3(grid), dim3(block), [=]() { kernel(__VA_ARGS__); }))
 
 static inline void __syncthreads() { asm volatile("" ::: "memory"); hipemu_syncthreads(); asm volatile("" ::: "memory"); }
 static inline int hipemu_lane() { return (int)((threadIdx.x + threadIdx.y * blockDim.x) & 63); }

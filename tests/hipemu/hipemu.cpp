@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <string>
 #include <utility>
+#include <deque>
 
 hipemu_idx threadIdx, blockIdx, blockDim, gridDim;
 
@@ -169,22 +170,22 @@ hipError_t new_stream(hipStream_t* s, unsigned flags, int priority)
 }
 
 hipError_t hipMalloc(void** p, size_t n) { return new_block(LIVE_DEV, p, n); }
-hipError_t hipFree(void* p) { if (p) { gone(LIVE_DEV, p); free(p); } return hipSuccess; }
+hipError_t hipFree(void* p) { hipemu_drain(); if (p) { gone(LIVE_DEV, p); free(p); } return hipSuccess; }
 hipError_t hipHostMalloc(void** p, size_t n, unsigned) { return new_block(LIVE_HOST, p, n); }
-hipError_t hipHostFree(void* p) { if (p) { gone(LIVE_HOST, p); free(p); } return hipSuccess; }
+hipError_t hipHostFree(void* p) { hipemu_drain(); if (p) { gone(LIVE_HOST, p); free(p); } return hipSuccess; }
 hipError_t hipStreamCreate(hipStream_t* s) { return new_stream(s, 0, 0); }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned flags) { return new_stream(s, flags, 0); }
 hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned flags, int priority) { return new_stream(s, flags, priority); }
-hipError_t hipStreamDestroy(hipStream_t s) { gone(LIVE_STREAM, s); delete static_cast<StreamObj*>(s); return hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t s) { if (hipemu_held(s)) hipemu_hold_none(); gone(LIVE_STREAM, s); delete static_cast<StreamObj*>(s); return hipSuccess; }
 hipError_t hipEventCreate(hipEvent_t* e)
 {
     std::lock_guard<std::mutex> l(g_live_mutex);
-    *e = new hipemu_event{{}, g_events_created++};
+    *e = new hipemu_event{{}, g_events_created++, 0};
     g_live[LIVE_EVENT].insert(*e);
     return hipSuccess;
 }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
-hipError_t hipEventDestroy(hipEvent_t e) { gone(LIVE_EVENT, e); delete e; return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t e) { hipemu_drain_event(e); gone(LIVE_EVENT, e); delete e; return hipSuccess; }
 
 extern "C" void hipemu_live_counts(int64_t out[4])
 {
@@ -219,3 +220,32 @@ void hipemu_trace_op(const char* op, hipStream_t s, hipEvent_t e, const char* ke
     g_trace += std::string(op) + " " + name('s', !s, s ? static_cast<StreamObj*>(s)->id - g_trace_stream0 : 0) + " " + name('e', !e, e ? e->id - g_trace_event0 : 0) + " "
              + (kernel ? kernel : "-") + " " + dims + " " + (bytes ? std::to_string(bytes) : std::string("-")) + "\n";
 }
+
+// ---- one held stream (hip_runtime.h): its ops wait here, in order, until something the runtime orders behind them is met
+namespace {
+struct HeldOp { std::function<void()> run; hipEvent_t recorded; };
+std::deque<HeldOp> g_held;
+int64_t g_hold_index = -1;
+void run_front()
+{
+    HeldOp op = std::move(g_held.front());
+    g_held.pop_front();
+    op.run();
+    if (op.recorded) op.recorded->queued--;
+}
+}
+bool hipemu_held(hipStream_t st) { return st && g_hold_index >= 0 && static_cast<StreamObj*>(st)->id - g_trace_stream0 == g_hold_index; }
+void hipemu_defer(std::function<void()> op, hipEvent_t recorded)
+{
+    if (recorded) recorded->queued++;
+    g_held.push_back(HeldOp{std::move(op), recorded});
+}
+void hipemu_drain() { while (!g_held.empty()) run_front(); }
+void hipemu_drain_event(hipEvent_t e) { while (e && e->queued > 0) run_front(); }
+void hipemu_launch_on(hipStream_t st, dim3 grid, dim3 block, std::function<void()> body)
+{
+    if (hipemu_held(st)) hipemu_defer([grid, block, body = std::move(body)]() { hipemu_launch(grid, block, body); });
+    else hipemu_launch(grid, block, body);
+}
+extern "C" void hipemu_hold_stream(int64_t index) { hipemu_drain(); g_hold_index = index; }
+extern "C" void hipemu_hold_none() { hipemu_drain(); g_hold_index = -1; }

@@ -318,14 +318,9 @@ def check_live_raw_vs_oracle(d_factory, fmt, nf=9, seed=5, snr_db=18, cfo=-35, a
 
 
 # ---- DAB+ superframe filter on the device vs the oracle's (itself pinned to the real SuperframeFilter)
-def check_superframes_vs_oracle(d_factory, F=3, nf=16, snr_db=5.0, seed=12, B=2, damage=True, auto_modes=(False, True), cfo=20, stats=None, min_synced=1,
-                                ensemble=None, pick=(1, 6), damage_q=(6, 8), payload_fn=None):
-    """superframes straddle the batches (12 logical frames per batch, 5 per superframe); the noise level makes the Viterbi
-    output carry byte errors for Reed-Solomon to correct (no loss of lock: batch mode and the reference drop different
-    frames then), and the transmitter damages some superframes beyond repair: a broken access unit, more byte errors than
-    RS(120,110) corrects, a Fire-code hit that costs the synchronisation.  payload_fn: another payload for the whole ensemble instead
-    (the caller then asserts on its own what it meant to cover; stats gets the oracle's events per picked sub-channel and the first
-    logical frame the oracle emitted)"""
+def damaged_dabplus_payload(seed, damage=True, damage_q=(6, 8)):
+    """DAB+ payload (period 80 logical frames) whose superframes damage_q[0] and damage_q[1] of the period the transmitter damages beyond
+    repair: a broken access unit with a code word beyond the RS capacity; a header column lost, so that the Fire code fails and the window slides"""
     base = synth.dabplus_payload_fn(80, seed)
 
     def payload(sc, r):
@@ -339,6 +334,18 @@ def check_superframes_vs_oracle(d_factory, F=3, nf=16, snr_db=5.0, seed=12, B=2,
             if q == damage_q[1] and k == 0:
                 for j in range(4, 10): data[j * (sc.bitrate // 8)] ^= 0x81           # header column uncorrectable -> Fire code fails -> window slides
         return bytes(data)
+    return payload
+
+
+def check_superframes_vs_oracle(d_factory, F=3, nf=16, snr_db=5.0, seed=12, B=2, damage=True, auto_modes=(False, True), cfo=20, stats=None, min_synced=1,
+                                ensemble=None, pick=(1, 6), damage_q=(6, 8), payload_fn=None):
+    """superframes straddle the batches (12 logical frames per batch, 5 per superframe); the noise level makes the Viterbi
+    output carry byte errors for Reed-Solomon to correct (no loss of lock: batch mode and the reference drop different
+    frames then), and the transmitter damages some superframes beyond repair: a broken access unit, more byte errors than
+    RS(120,110) corrects, a Fire-code hit that costs the synchronisation.  payload_fn: another payload for the whole ensemble instead
+    (the caller then asserts on its own what it meant to cover; stats gets the oracle's events per picked sub-channel and the first
+    logical frame the oracle emitted)"""
+    payload = damaged_dabplus_payload(seed, damage, damage_q)
     # ensemble: the sub-channels of the multiplex (default: 18 x 64 kbit/s); pick: the ones the filter is checked on
     x, tx = synth.make_stream(nf, snr_db=snr_db, cfo_hz=cfo, delay=50, return_tx=True, seed=seed, payload_fn=payload_fn or payload, subchs=ensemble)
     subs = [tx.subchs[i] for i in pick]
@@ -1489,3 +1496,335 @@ def check_impaired_stream(d_factory, channel, F, schedule, placement, snr_db=18,
     nf = nf or (3 * F + 4 if schedule == 0 else 4 * F + 5)
     check_stream_vs_oracle(d_factory, snr_db, cfo, delay, nf, lockstep, B=B, seed=seed, F=F, pipeline_sync=schedule, fft_placement=placement,
                            channel=CHANNELS[channel] if isinstance(channel, str) else channel)
+
+
+# ---------------------------------------------------------------------------------------------- the deferred superframe filter
+# dabphy_set_auto_superframes(2): "every batch is filtered exactly once either way, with the same results" (include/dabphy.h), batch by
+# batch.  The expected totals of a batch come from the ORACLE, never from another handle: SuperframeFilter is causal, so its totals over
+# the logical frames up to the end of batch k minus those up to the end of batch k - 1 are batch k's.
+def sf_totals(frames):
+    """oracle totals over logical frames [n][frame_bytes]: synchronised superframes, corrected symbols, uncorrectable attempts, access units failing their CRC"""
+    tot = np.zeros(4, np.int64)
+    if len(frames):
+        for e in R.orc_superframe_run(np.ascontiguousarray(frames))[0]:
+            tot += (e[3], e[1], e[2], (e[5] - bin(e[7]).count("1")) if e[3] else 0)
+    return tot
+
+
+class SfTrack:
+    """one service as one SuperframeFilter sees it: the oracle's logical frames from `first` on; advance(rows) takes the rows a batch
+    delivered (they must be the oracle's next ones) and returns the oracle's totals of that batch -- the filter run on the two prefixes"""
+
+    def __init__(self, msc_bytes, frame_bytes, first=0):
+        f = np.frombuffer(bytes(msc_bytes), np.uint8)
+        self.fr = f[:len(f) // frame_bytes * frame_bytes].reshape(-1, frame_bytes)[first:]
+        self.n = 0; self.tot = np.zeros(4, np.int64)
+
+    def advance(self, rows):
+        n = len(rows)
+        assert self.n + n <= len(self.fr) and np.array_equal(rows, self.fr[self.n:self.n + n]), "logical frames %d .. %d differ from the oracle's" % (self.n, self.n + n)
+        self.n += n
+        tot = sf_totals(self.fr[:self.n])
+        batch = tot - self.tot; self.tot = tot
+        return batch
+
+
+def drive_deferred(d, calls, tracks_of, before=None, each=None):
+    """process(calls[k]) for every k, superframes_stats() ONCE behind each; tracks_of(k, info)[b] = the SfTracks of ensemble b's list in call k
+    (None: a position the DAB+ filter leaves out), before[k](d, want, got): what happens in front of call k (it may append to got what it
+    fetches), each(d, k): after every call.
+    -> (want[k] = oracle totals of batch k [B][4], got[k] = what the k-th fetch returned, infos[k] = frame_info of batch k)"""
+    want, got, infos = [], [], []
+    for k, Fk in enumerate(calls):
+        if before and k in before:
+            before[k](d, want, got)
+        d.process(Fk)
+        info = d.frame_info()
+        tracks = tracks_of(k, info)
+        wb = np.zeros((len(tracks), 4), np.int64)
+        for b, trs in enumerate(tracks):
+            nv = int((info[b, :Fk]["valid"] == 1).sum())
+            for idx, tr in enumerate(trs):
+                m, fv, nr = d.msc_ensemble(b, idx)
+                assert nr == 4 * nv, (k, b, idx, nr, nv)
+                if tr is not None:
+                    wb[b] += tr.advance(m[fv:nr])
+        want.append(wb); infos.append(info[:, :Fk].copy())
+        got.append(d.superframes_stats().astype(np.int64))
+        if each:
+            each(d, k)
+    return want, got, infos
+
+
+def assert_deferred_sequence(d, want, got, first=0):
+    """mode 2 from call `first` on, one fetch per call: zeros behind the first call, batch k's totals behind call k + 1, the last batch's from
+    one extra call, zeros from the call after that"""
+    assert not got[first].any(), "the fetch behind the first process() returned %s, not zeros" % got[first].tolist()
+    for k in range(first, len(want) - 1):
+        assert np.array_equal(got[k + 1], want[k]), "totals fetched behind call %d: %s, the oracle's totals of batch %d: %s" % (k + 1, got[k + 1].tolist(), k, want[k].tolist())
+    last = d.superframes_stats()
+    assert np.array_equal(last, want[-1]), "the extra fetch at the end: %s, the oracle's totals of the last batch: %s" % (last.tolist(), want[-1].tolist())
+    assert not d.superframes_stats().any(), "a fetch with nothing pending returned totals"
+    assert np.array_equal(sum(got[first:]) + last, sum(want[first:]))
+
+
+DEFERRED_RATES = (16, 40, 64)      # three DAB+ sub-channels: 2 / 5 / 8 code words per superframe, logical frames of 48 / 120 / 192 bytes
+_deferred_streams = {}
+
+
+def deferred_stream(nf=16, snr_db=5.0, seed=12, cfo=20, damage_q=(6, 8)):
+    """the damaged DAB+ stream of check_superframes_vs_oracle on a small ensemble, watched from its first sample; computed once.
+    -> (samples, sub-channels, oracle run)"""
+    key = (nf, snr_db, seed, cfo, damage_q)
+    if key not in _deferred_streams:
+        subchs, cu = [], 0
+        for i, br in enumerate(DEFERRED_RATES):
+            sc = synth.SubchannelCfg(i + 1, cu, br, False, 3); subchs.append(sc); cu += sc.size_cu
+        x = synth.make_stream(nf, snr_db=snr_db, cfo_hz=cfo, delay=50, seed=seed, payload_fn=damaged_dabplus_payload(seed, True, damage_q), subchs=subchs)
+        x = np.asarray(x, np.complex64); x.setflags(write=False)
+        _deferred_streams[key] = (x, subchs, R.orc_receiver_run(x, subchs=subchs))
+    return _deferred_streams[key]
+
+
+def open_deferred(d_factory, x, subchs, B, max_frames, mode=2, **cfg):
+    d = d_factory(n_ensembles=B, max_frames=max_frames, want_constellation=False, **cfg)
+    try:
+        d.stream_upload(np.tile(x, (B, 1)))
+        d.set_subchannels([(s.subch_id, s.start_cu, s.size_cu, dev_prot(d, s)) for s in subchs])
+        d.set_auto_superframes(mode)
+    except Exception:
+        d.close()
+        raise
+    return d
+
+
+def stream_conditions(want, infos, fill=True, invalid=True, straddle=False):
+    """on the oracle's numbers and frame_info() only: every column of the totals is met; a batch behind the first lies inside the 16-CIF
+    fill of the time de-interleavers (the first one does by construction) and -- straddle -- a batch begins inside the fill and ends
+    beyond it: it carries rows, and c0 - cif0 < 16 decides which (r_first); a batch holds an invalid frame"""
+    total = sum(want)
+    assert (total > 0).all(), "a column of the oracle's totals is zero over the run: %s" % total.tolist()
+    v = [i[0]["valid"] == 1 for i in infos]
+    k0 = next(k for k, m in enumerate(v) if m.any())
+    cif0 = 4 * int(infos[k0][0]["frame_no"][v[k0]][0])
+    spans = [(4 * int(i[0]["frame_no"][m][0]) - cif0, 4 * int(i[0]["frame_no"][m][0]) - cif0 + 4 * int(m.sum())) for i, m in zip(infos, v) if m.any()]
+    assert not fill or any(0 < c0 < 16 for c0, c1 in spans), "no batch behind the first inside the fill: %s" % spans
+    assert not straddle or any(c0 < 16 < c1 for c0, c1 in spans), "no batch straddles the end of the fill: %s" % spans
+    assert not invalid or any(not m.all() for m in v), "no batch holds an invalid frame"
+
+
+def check_deferred_superframes(d_factory, pipeline_sync, F, sync_early=0, nf=16, B=2, mode=2):
+    """Per-batch contract of the deferred filter on one schedule: the damaged stream from its first sample (batches inside the fill, where
+    c0 - cif0 < 16 decides which rows are fed), to beyond its end (batches with starved frame slots: n_rows follows `valid`).
+    mode = 1: the same stream and oracle rule with the filter inside process() (totals behind the same call)."""
+    x, subchs, o = deferred_stream(nf)
+    d = open_deferred(d_factory, x, subchs, B, F, mode=mode, pipeline_sync=pipeline_sync, sync_early=sync_early)
+    try:
+        tracks = [[SfTrack(o["msc"][i], sc.frame_bytes) for i, sc in enumerate(subchs)] for _ in range(B)]
+        want, got, infos = drive_deferred(d, [F] * ((nf + F - 1) // F + 1), lambda k, info: tracks)
+        stream_conditions(want, infos, straddle=F == 3)         # (F = 1: the fill ends between two batches)
+        if mode == 2:
+            assert_deferred_sequence(d, want, got)
+        else:
+            for k in range(len(want)):
+                assert np.array_equal(got[k], want[k]), "batch %d: totals %s, the oracle's %s" % (k, got[k].tolist(), want[k].tolist())
+        assert tracks[0][0].n >= 4 * (o["n_frames"] - F * (1 + {0: 0, 1: 1, 2: 1, 3: 2}[int(pipeline_sync)])) - 16, tracks[0][0].n      # (as check_stream_vs_oracle)
+    finally:
+        d.close()
+    return want
+
+
+def fresh_tracks(subchs, o, B):
+    return [[SfTrack(o["msc"][i], sc.frame_bytes) for i, sc in enumerate(subchs)] for _ in range(B)]
+
+
+def door_growing_frames(d_factory):
+    """n_frames grows and shrinks from call to call (pipeline_sync = 0): a deeper batch reallocates the class outputs the pending pass reads.
+    (They hold whole groups of 64 code words, 4 per frame and ensemble: with five ensembles 2 -> 5 frames is one group -> two, it grows;
+    the batch pending then is the third: beyond the fill, so its pass feeds rows.)"""
+    x, subchs, o = deferred_stream(16)
+    d = open_deferred(d_factory, x, subchs, 5, 5, pipeline_sync=0)
+    try:
+        tracks = fresh_tracks(subchs, o, 5)
+        calls = [2, 2, 2, 5, 3, 5, 1, 2]
+        want, got, infos = drive_deferred(d, calls, lambda k, info: tracks)
+        stream_conditions(want, infos)
+        # the growth (the first call of five frames) meets a pending pass that feeds rows: its batch lies beyond the fill, all its frames
+        # are valid, and the oracle's totals of it are not zero -- a pass that read a fresh buffer could not return them
+        g = calls.index(5)
+        assert max(calls[:g]) * 4 * 5 <= 64 < 5 * 4 * 5 and (infos[g - 1][:, :]["valid"] == 1).all() and want[g - 1].any(axis=1).all(), (want[g - 1].tolist(), infos[g - 1]["valid"].tolist())
+        assert 4 * (int(infos[g - 1][0, 0]["frame_no"]) - int(infos[0][0, 0]["frame_no"])) >= 16
+        assert_deferred_sequence(d, want, got)
+    finally:
+        d.close()
+
+
+def door_mode_switches(d_factory, F=2):
+    """2 -> 1 -> 2 -> 0 in mid-stream, each switch with a pass pending or just fetched: every batch's totals reach the caller exactly once"""
+    x, subchs, o = deferred_stream(16)
+    d = open_deferred(d_factory, x, subchs, 2, F, pipeline_sync=1)
+    try:
+        tracks = fresh_tracks(subchs, o, 2)
+        extra = {}
+
+        def switch(mode, fetch):
+            def fn(d, want, got):
+                d.set_auto_superframes(mode)
+                if fetch:
+                    extra[len(want)] = d.superframes_stats().astype(np.int64)       # (what leaving mode 2 ran: the batch before this call)
+            return fn
+        want, got, infos = drive_deferred(d, [F] * 8, lambda k, info: tracks, before={3: switch(1, True), 5: switch(2, False), 7: switch(0, True)})
+        stream_conditions(want, infos, invalid=False)
+        zero = np.zeros_like(want[0])
+        # calls 0-2 in mode 2 (zeros, batch 0, batch 1; the switch fetches batch 2), 3-4 in mode 1 (their own), 5-6 in mode 2 (zeros -- batch 4 was
+        # filtered in its call --, batch 5; the switch fetches batch 6), 7 in mode 0 (its own)
+        expect = [zero, want[0], want[1], want[3], want[4], zero, want[5], want[7]]
+        for k in range(8):
+            assert np.array_equal(got[k], expect[k]), "fetch behind call %d: %s, expected %s" % (k, got[k].tolist(), expect[k].tolist())
+        assert np.array_equal(extra[3], want[2]) and np.array_equal(extra[7], want[6]), (extra, want[2].tolist(), want[6].tolist())
+        assert np.array_equal(sum(got) + extra[3] + extra[7], sum(want))
+    finally:
+        d.close()
+
+
+def door_reset(d_factory, F=2):
+    """dabphy_reset with a pass pending: it is dropped (zeros), and the stream that starts over is filtered from fresh windows"""
+    x, subchs, o = deferred_stream(16)
+    d = open_deferred(d_factory, x, subchs, 2, F, pipeline_sync=1)
+    try:
+        tracks = fresh_tracks(subchs, o, 2)
+        want, got, infos = drive_deferred(d, [F] * 6, lambda k, info: tracks)
+        assert sum(want).any() and not got[0].any() and all(np.array_equal(got[k + 1], want[k]) for k in range(5))
+        d.reset()
+        assert not d.superframes_stats().any(), "totals after dabphy_reset"
+        tracks = fresh_tracks(subchs, o, 2)
+        want, got, infos = drive_deferred(d, [F] * 9, lambda k, info: tracks)
+        stream_conditions(want, infos)
+        assert_deferred_sequence(d, want, got)
+    finally:
+        d.close()
+
+
+def door_service_changes(d_factory, F=2, nf=20, add_step=3, remove_step=6):
+    """the stream of check_service_changes_in_mid_stream under mode 2: ensemble 0 plays A and B, adds D, drops A; ensemble 1 plays C.  The
+    pass pending at a change belongs to the old lists (it is run before they are rebuilt); D's filter starts with its first frame"""
+    xs, txs = [], []
+    for e in range(2):
+        x, tx = synth.make_stream(nf, eid=0x4000 + e, snr_db=5.5, cfo_hz=(35, -60)[e], delay=(40, 700)[e], return_tx=True, seed=90 + e,
+                                  payload_fn=synth.dabplus_payload_fn(80, 5 + e), noise_seed=78)
+        xs.append(x); txs.append(tx)
+    n = min(len(x) for x in xs)
+    xs = [x[:n] for x in xs]
+    A, Bc, D, Cc = txs[0].subchs[2], txs[0].subchs[7], txs[0].subchs[12], txs[1].subchs[4]
+    o0 = R.orc_receiver_run(xs[0], subchs=[A, Bc, D]); o1 = R.orc_receiver_run(xs[1], subchs=[Cc])
+    d = d_factory(n_ensembles=2, max_frames=F, want_constellation=False, pipeline_sync=1)
+    sub = lambda s: (s.subch_id, s.start_cu, s.size_cu, dev_prot(d, s))
+    try:
+        d.stream_upload(np.stack(xs))
+        d.set_subchannels_ensemble(0, [sub(A), sub(Bc)]); d.set_subchannels_ensemble(1, [sub(Cc)])
+        d.set_auto_superframes(2)
+        tr = {"A": SfTrack(o0["msc"][0], A.frame_bytes), "B": SfTrack(o0["msc"][1], Bc.frame_bytes), "C": SfTrack(o1["msc"][0], Cc.frame_bytes)}
+
+        def tracks_of(k, info):
+            if k == add_step:       # D's first logical frame is the one of CIF (first CIF of this batch) + 16: the oracle's frame of that index
+                tr["D"] = SfTrack(o0["msc"][2], D.frame_bytes, first=4 * int(info[0, 0]["frame_no"]))
+            names = ("A", "B") if k < add_step else ("A", "B", "D") if k < remove_step else ("B", "D")
+            return [[tr[n] for n in names], [tr["C"]]]
+        before = {add_step: lambda d, w, g: d.set_subchannels_ensemble(0, [sub(A), sub(Bc), sub(D)]), remove_step: lambda d, w, g: d.set_subchannels_ensemble(0, [sub(Bc), sub(D)])}
+        want, got, infos = drive_deferred(d, [F] * ((nf + F - 1) // F), tracks_of, before=before)
+        assert tr["D"].n >= 8 and (sum(want)[:, :2] > 0).all(), (tr["D"].n, sum(want).tolist())
+        assert_deferred_sequence(d, want, got)
+    finally:
+        d.close()
+
+
+def door_mp2(d_factory, F=3, nf=15, B=2):
+    """set_auto_mp2 together with mode 2 (tests/mp2_chain.py's ensemble: three MP2 services, two DAB+): the DAB+ totals per batch against the
+    oracle, the MP2 events against the model on the bytes the device decoded"""
+    import mp2_chain
+    from welle_io_amd import capi
+    subchs, payload = mp2_chain.ensemble()
+    x = np.asarray(synth.make_stream(nf, snr_db=6.0, cfo_hz=20, delay=50, seed=3, payload_fn=payload, subchs=subchs), np.complex64)
+    o = R.orc_receiver_run(x, subchs=subchs)
+    kinds = [capi.AUDIO_MP2 if s[2] else capi.AUDIO_DABPLUS for s in mp2_chain.SERVICES]
+    d = d_factory(n_ensembles=B, max_frames=F, want_constellation=False, pipeline_sync=1)
+    try:
+        d.stream_upload(np.tile(x, (B, 1)))
+        d.set_subchannels([(s.subch_id, s.start_cu, s.size_cu, dev_prot(d, s)) for s in subchs])
+        for b in range(B):
+            d.set_audio_kinds_ensemble(b, kinds)
+        d.set_auto_mp2(True); d.set_auto_superframes(2)
+        tracks = [[None if kinds[i] else SfTrack(o["msc"][i], sc.frame_bytes) for i, sc in enumerate(subchs)] for _ in range(B)]
+        checks = {}; mp2_tot = np.zeros((B, 4), np.int64)
+
+        def each(d, k):
+            mp2_tot[:] += d.mp2_stats()
+            for i in range(len(subchs)):
+                if kinds[i]:
+                    out, fv = d.msc(i)
+                    for b in range(B):
+                        ev, n, fe, fu = d.mp2_frames_ensemble(b, i)
+                        checks.setdefault((b, i), mp2_chain.ServiceCheck()).batch(out[b, fv[b]:d.msc_rows[b]], int(fv[b]), ev, n, fe, fu)
+        want, got, infos = drive_deferred(d, [F] * (nf // F), lambda k, info: tracks, each=each)
+        assert (sum(want)[:, 0] > 0).all(), sum(want).tolist()
+        assert_deferred_sequence(d, want, got)
+        models = [c.verify() for c in checks.values()]
+        assert len(models) == 3 * B and mp2_tot[:, 0].min() > 0 and int(mp2_tot[:, 0].sum()) == sum(len(m.events) for m in models)
+    finally:
+        d.close()
+
+
+def door_replay(d_factory, pipeline_sync, F=4, nf=25):
+    """exact batch mode decodes a batch twice (3 dB, -1000 Hz, seed 5) with the filter deferred: the replayed batch's pass has not run when
+    the batch is put back, and runs once, on its final bytes"""
+    x, tx = synth.make_stream(nf, snr_db=3, cfo_hz=-1000, delay=150, return_tx=True, seed=5)
+    x = np.asarray(x, np.complex64)
+    subchs = [tx.subchs[0], tx.subchs[5], tx.subchs[9]]
+    o = R.orc_receiver_run(x, subchs=subchs)
+    d = open_deferred(d_factory, x, subchs, 1, F, pipeline_sync=pipeline_sync)
+    try:
+        tracks = fresh_tracks(subchs, o, 1)
+        want, got, infos = drive_deferred(d, [F] * (nf // F), lambda k, info: tracks)
+        assert d.replayed_batches() >= 1, "no batch was decoded twice"
+        assert sum(want).any() and tracks[0][0].n >= 4 * (nf - 3 * F) - 16, (sum(want).tolist(), tracks[0][0].n)
+        assert_deferred_sequence(d, want, got)
+    finally:
+        d.close()
+
+
+def door_dropout(d_factory, F=4):
+    """the dropout of check_dropout_batch on schedule 3: failed window searches and a re-acquisition inside the batches whose descriptors the
+    pending pass reads while the synchroniser is two batches ahead"""
+    T_F = 196608
+    x, tx = synth.make_stream(20, snr_db=18, cfo_hz=60, delay=200, seed=8, return_tx=True, payload_fn=synth.dabplus_payload_fn(80, 8))
+    x = np.asarray(x, np.complex64).copy()
+    x[6 * T_F + 50000:7 * T_F + 120000] = 0
+    subchs = [tx.subchs[1], tx.subchs[4]]
+    o = R.orc_receiver_run(x, subchs=subchs, disable_coarse=True)
+    assert o["n_sync_false"] > 5 and o["n_frames"] >= 16
+    d = open_deferred(d_factory, x, subchs, 1, F, pipeline_sync=3, disable_coarse=True)
+    try:
+        tracks = fresh_tracks(subchs, o, 1)
+        want, got, infos = drive_deferred(d, [F] * 8, lambda k, info: tracks)
+        v = [i[0]["valid"] for i in infos]
+        assert any((m == 3).any() and (m == 1).any() for m in v), [m.tolist() for m in v]       # a failed search and frames in one batch
+        assert sum(want)[0, 0] > 0 and tracks[0][0].n >= 4 * (o["n_frames"] - 3 * F) - 16, (sum(want).tolist(), tracks[0][0].n)
+        assert_deferred_sequence(d, want, got)
+    finally:
+        d.close()
+
+
+DEFERRED_SIDE_DOORS = {
+    "growing_n_frames": door_growing_frames,
+    "service_changes": door_service_changes,
+    "mode_switches": door_mode_switches,
+    "auto_mp2": door_mp2,
+    "replay_schedule_0": lambda f: door_replay(f, 0),
+    "replay_schedule_1": lambda f: door_replay(f, 1),
+    "dropout_schedule_3": door_dropout,
+    "reset": door_reset,
+}
+
+
+def check_deferred_side_door(d_factory, name):
+    DEFERRED_SIDE_DOORS[name](d_factory)

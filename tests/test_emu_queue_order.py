@@ -55,6 +55,7 @@ SCENARIOS = {
     "replay_state_parallel": (dict(pipeline_sync=0, decode_shape=2), 4, 3, plain, {}, True),
     "auto_superframes_1": (dict(pipeline_sync=0), 3, 4, lambda d: d.set_auto_superframes(1), {}, False),
     "auto_superframes_2": (dict(pipeline_sync=1), 3, 4, lambda d: d.set_auto_superframes(2), {}, False),
+    "auto_superframes_2_schedule_3": (dict(pipeline_sync=3), 3, 4, lambda d: d.set_auto_superframes(2), {}, False),
     "auto_mp2": (dict(pipeline_sync=0), 3, 4, None, {}, False),
     "tii": (dict(pipeline_sync=0), 3, 4, lambda d: d.set_tii(True), {}, False),
     "two_kernel_msc": (dict(pipeline_sync=0), 3, 3, plain, {"DABPHY_FUSED_MSC": "0"}, False),

@@ -192,9 +192,10 @@ def test_benchmark_handle_configuration_small(emu):
 
 
 def test_benchmark_configuration_with_the_deferred_filter(emu):
-    """dabphy_set_auto_superframes(2), what bench.py's handle runs with: the superframe filter pass of a batch is queued by the NEXT
-    dabphy_process beside its FFT stage; the totals arrive one batch later and sum to the same (the oracle's); with the synchroniser
-    behind the decoder as in rounds 1-5 (dabphy_config.sync_early = 1; every other test runs the default: in front)"""
+    """dabphy_set_auto_superframes(2) on the handle bench.py opens (bench.py itself keeps mode 1: the deferred pass was a measured loss,
+    DESIGN.md section 4.5): the superframe filter pass of a batch is queued by the NEXT dabphy_process beside its FFT stage; the totals
+    arrive one batch later and sum to the same (the oracle's); with the synchroniser behind the decoder as in rounds 1-5
+    (dabphy_config.sync_early = 1).  Batch by batch, on every schedule: test_deferred_superframe_filter below."""
     from welle_io_amd import workload
     base = workload.make_base_streams(2, workload.REC_FRAMES, seed0=0)
     P.check_bench_config(capi, EMU_LIB, 3, 3, 1, check_ens=[0, 2], n_steps=5, demod_chunk=25, device="cpu", subs_idx=(0, 7, 17), base=base, expect_chunk=25, decode_shape=1,
@@ -365,3 +366,21 @@ def test_service_changes_with_two_code_words_per_wavefront(emu):
     """services changing in mid-stream through k_viterbi_sp2 + k_traceback_sp2 (decode_shape = 2: what batches of 1 024 .. 40 960 code words
     take on the device)"""
     P.check_service_changes_in_mid_stream(factory_state_parallel)
+
+
+@pytest.mark.parametrize("F", [1, 3])
+@pytest.mark.parametrize("sync_early", [0, 1])
+@pytest.mark.parametrize("pipeline_sync", [0, 1, 2, 3])
+def test_deferred_superframe_filter(emu, pipeline_sync, sync_early, F):
+    """dabphy_set_auto_superframes(2), batch by batch against the oracle: superframes_stats() behind process(k + 1) returns batch k's totals,
+    zeros behind the first call, the last batch's from one extra call, zeros after that -- a damaged DAB+ stream watched from its first
+    sample (batches inside the 16-CIF fill) to beyond its end (starved frame slots), on every schedule, with the next chains queued in
+    front of the decoder (sync_early = 0) and behind it"""
+    P.check_deferred_superframes(factory, pipeline_sync, F, sync_early=sync_early)
+
+
+@pytest.mark.parametrize("name", sorted(P.DEFERRED_SIDE_DOORS))
+def test_deferred_superframe_filter_side_doors(emu, name):
+    """what runs or drops the pending pass: another n_frames, a change of the sub-channel lists, a change of mode, the MP2 pass, a replayed
+    batch, a dropout, dabphy_reset (tests/parity_cases.py: door_*)"""
+    P.check_deferred_side_door(factory, name)

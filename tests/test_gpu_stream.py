@@ -376,3 +376,16 @@ def test_service_changes_while_the_synchroniser_runs_ahead(gpu, mode):
     """selection changes between dabphy_process calls with the pipelined schedules: they apply to the batch decoded next, whatever has been
     synchronised ahead; bytes and superframe events of the services that stay = the uninterrupted oracle's"""
     P.check_service_changes_in_mid_stream(factory, pipeline_sync=mode)
+
+
+@pytest.mark.parametrize("pipeline_sync", [0, 1, 2, 3])
+@pytest.mark.parametrize("F", [1, 3])
+def test_deferred_superframe_filter(gpu, pipeline_sync, F):
+    """dabphy_set_auto_superframes(2) on the real runtime: the pass of batch k queued by process(k + 1) on the auxiliary stream; per batch
+    the oracle's totals, one call late (twin of tests/test_emu_stream.py; pins the contract, does not try to make a race appear)"""
+    P.check_deferred_superframes(factory, pipeline_sync, F)
+
+
+@pytest.mark.parametrize("name", sorted(P.DEFERRED_SIDE_DOORS))
+def test_deferred_superframe_filter_side_doors(gpu, name):
+    P.check_deferred_side_door(factory, name)

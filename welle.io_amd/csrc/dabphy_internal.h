@@ -203,7 +203,17 @@ struct dabphy_handle {
     bool tii_on = false; bool tii_ran = false;
     bool track_slevel = false;        // dabphy_set_track_slevel: sLevel follows every tracked frame instead of catching up at a loss of lock
     // dabphy_set_auto_superframes(2): the filter pass of batch k runs beside batch k + 1's FFT stage, on a stream of its own
+    //   state of batch k's pass      pending  inflight  unfetched   set by
+    //   decoded, pass not queued        1        0         -        dabphy_process(k), at its end (sf_def_desc / sf_def_frames name the batch)
+    //   queued on rs_stream             0        1         1        launch_deferred_superframes: dabphy_process(k + 1), a flush, a second fetch
+    //   waited for                      0        0         1        the end of dabphy_process(k + 1); hipEventSynchronize in a flush or a fetch
+    //   totals handed to the caller     0        0         0        dabphy_superframes_stats
+    //   polled: a fetch has been made since the last dabphy_process -- the next one runs a pending pass at once (the end of a stream).
+    //   flush (run now, wait): another sub-channel list or audio kinds, another n_frames, leaving the mode -- which parks unfetched totals
+    //   in h_sf_stats for the next fetch (sf_stats_ready + h_sf_stats_valid) so that the new mode does not filter the batch again.
+    //   dabphy_reset clears all of it.
     bool sf_deferred = false, sf_def_pending = false, sf_def_unfetched = false, sf_def_inflight = false;
+    bool sf_def_polled = false;             // dabphy_superframes_stats has been called since the last dabphy_process (the next call runs the pending pass)
     const FrameDesc* sf_def_desc = nullptr; uint32_t sf_def_frames = 0;
     hipStream_t rs_stream = nullptr; hipEvent_t ev_rs_done = nullptr;
     bool sf_auto = false, sf_stats_ready = false;   // dabphy_set_auto_superframes: the all-sub-channel filter rides in dabphy_process's submission

@@ -210,6 +210,10 @@ static int queue_next_chains(dabphy_handle* h, const Batch& b)
 {
     int r;
     if (h->cfg.pipeline_sync != 2) HIPCHK(h, hipStreamWaitEvent(h->sync_stream, h->ev_chain_gate, 0));
+    // (dabphy_set_auto_superframes(2): TWO batches ahead -- only then: N_DESC = 3 --, the chain queued here writes the descriptor buffer of
+    // the PREVIOUS batch, whose filter pass -- launched earlier in this call, decode_batch -- reads valid / frame_no from it: the chain
+    // waits for that pass.  One batch ahead the chain writes another buffer and waits for nothing)
+    if (b.depth == 2 && h->sf_def_inflight && h->ahead < 1 + b.depth) HIPCHK(h, hipStreamWaitEvent(h->sync_stream, h->ev_rs_done, 0));
     for (; h->ahead < 1 + b.depth; h->ahead++) if ((r = queue_chain(h, (b.cur + h->ahead) % dabphy_handle::N_DESC, b.F))) return r;
     return 0;
 }
@@ -333,6 +337,9 @@ static int decode_batch(dabphy_handle* h, Batch& b, const bool replay)
     // (cfg.sync_early: in front of the decoder (0, the default: neutral on the headline, 0.2 ms on a batch of drifting ensembles, whose
     // window searches run one after the other in the find chain -- latency-bound work for one work-group per ensemble that belongs beside the
     // decoder); behind it (1); in front only while the last pass met ensembles whose window moves (2); 3: an experiment, see below)
+    // dabphy_set_auto_superframes(2), two batches ahead: the PREVIOUS batch's filter pass in front of the next chains, one of which reuses
+    // the descriptors it reads and has to wait for it (queue_next_chains); on the other schedules it keeps its place below
+    if (!replay && b.depth == 2 && h->sf_auto && h->sf_deferred && (r = launch_deferred_superframes(h))) return r;
     const bool early = h->chain_early || (h->cfg.pipeline_sync != 2 && (h->cfg.sync_early == 0 || h->cfg.sync_early == 3 || (h->cfg.sync_early == 2 && h->drift_seen)));
     if (!replay && b.depth && early) {
         // the next batch's synchroniser is handed to the device BEFORE this batch's decoder (whose persistent waves would otherwise hold
@@ -344,8 +351,8 @@ static int decode_batch(dabphy_handle* h, Batch& b, const bool replay)
         // proper, ~0.8 ms of throughput work that then has the device to itself; the find chain's rounds run beside the decoder)
         if (h->cfg.sync_early == 3 && h->wide_front_recorded) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_wide_front, 0));
     }
-    // dabphy_set_auto_superframes(2): the PREVIOUS batch's superframe filter pass, beside this batch's FFT stage; this batch's decoders
-    // wait for it on the device before they overwrite the class outputs it reads
+    // dabphy_set_auto_superframes(2): the PREVIOUS batch's superframe filter pass, beside this batch's FFT stage (nothing left to launch when
+    // it went in front of the chains above); this batch's decoders wait for it on the device before they overwrite the class outputs it reads
     if (!replay && h->sf_auto && h->sf_deferred && (r = launch_deferred_superframes(h))) return r;
     if (h->sf_def_inflight) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_rs_done, 0));
     if ((r = queue_aux_work(h, b))) return r;
@@ -424,7 +431,9 @@ int dabphy_process(dabphy_handle* h, uint32_t n_frames)
     const uint32_t F = b.F = n_frames;
     b.B = h->cfg.n_ensembles; b.ring_frames = (int)h->cfg.max_frames + 5; b.ens_stride = soft_ens_stride(h);
     int r;
-    if (h->subch_dirty && (h->sf_def_pending || h->sf_def_inflight) && (r = flush_deferred_superframes(h))) return r;      // (the deferred filter pass of the last batch belongs to the classes that are about to be rebuilt)
+    // the deferred filter pass of the last batch belongs to the classes that are about to be rebuilt, and to class outputs of its own
+    // depth: another n_frames may grow them (reserve_batch: grow-only scratch, contents not kept) -- the pass runs now, and is waited for
+    if ((h->subch_dirty || n_frames != h->sf_def_frames) && (h->sf_def_pending || h->sf_def_inflight) && (r = flush_deferred_superframes(h))) return r;
     if ((r = apply_subchannels(h))) return r;                // per-ensemble sub-channel changes since the last batch (dabphy_set_subchannels_ensemble)
     if ((r = apply_audio_kinds(h))) return r;                // ... and audio kinds (dabphy_set_audio_kinds_ensemble)
     if ((r = reserve_batch(h, b))) return r;
@@ -465,7 +474,7 @@ int dabphy_process(dabphy_handle* h, uint32_t n_frames)
     if (h->sf_auto && h->sf_deferred) {
         // (the main stream has waited for the previous batch's pass: its totals are in host memory; this batch's pass is the next call's)
         h->sf_def_inflight = false;
-        h->sf_def_pending = true; h->sf_def_desc = b.d_desc; h->sf_def_frames = F;
+        h->sf_def_pending = true; h->sf_def_desc = b.d_desc; h->sf_def_frames = F; h->sf_def_polled = false;
     }
     // the host's mirror of the pair tables follows what k_pair_cif0 wrote (same rule, from the host's copy of the descriptors)
     for (auto& cls : h->classes) if (cls.cif0_pending) {

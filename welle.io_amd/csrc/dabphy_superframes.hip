@@ -299,7 +299,17 @@ int dabphy_set_auto_superframes(dabphy_handle* h, int32_t on)
 {
     DeviceBind dev_(h);
     if (!h) return DABPHY_ERR_INVALID;
-    if (h->sf_deferred && on != 2) { int r = flush_deferred_superframes(h); if (r) return r; }      // (leaving the deferred mode: nothing stays pending)
+    if (h->sf_deferred && on != 2) {
+        // leaving the deferred mode: nothing stays pending -- the last batch's pass runs now if it has not -- and the last batch is not
+        // filtered a second time by the mode that follows: its totals, unless they have been fetched (then zeros), are what the next
+        // dabphy_superframes_stats returns
+        int r = flush_deferred_superframes(h); if (r) return r;
+        if (h->last_frames && h->h_sf_stats) {
+            if (!h->sf_def_unfetched) memset(h->h_sf_stats, 0, sizeof(int32_t) * 4 * h->cfg.n_ensembles);
+            h->sf_stats_ready = h->h_sf_stats_valid = true;
+        }
+        h->sf_def_unfetched = h->sf_def_polled = false;
+    }
     h->sf_auto = on != 0;
     h->sf_deferred = on == 2;
     return DABPHY_OK;
@@ -308,18 +318,20 @@ int dabphy_set_auto_superframes(dabphy_handle* h, int32_t on)
 int dabphy_superframes_stats(dabphy_handle* h, int32_t* stats)
 {
     DeviceBind dev_(h);
-    if (!h || !stats || !h->last_frames || !h->last_desc) return DABPHY_ERR_INVALID;
+    if (!h || !stats) return DABPHY_ERR_INVALID;
     int r;
-    if (h->sf_auto && h->sf_deferred) {
-        // the totals of the pass that ran last and has not been fetched (the batch BEFORE the last dabphy_process); if there is none,
-        // the pending pass of the last batch runs now (the end of a stream: one more call fetches the last batch's totals)
-        if (!h->sf_def_unfetched && h->sf_def_pending) { if ((r = launch_deferred_superframes(h))) return r; }
+    if (h->sf_auto && h->sf_deferred) {      // (needs no batch: zeros when nothing is pending or unfetched, as after dabphy_reset)
+        // the first call after a dabphy_process: the totals of the pass that call queued (the batch BEFORE it), zeros if it queued
+        // none.  One more call without a dabphy_process in between: the pending pass of the last batch runs now (the end of a stream)
+        if (h->sf_def_polled && !h->sf_def_unfetched && h->sf_def_pending) { if ((r = launch_deferred_superframes(h))) return r; }
+        h->sf_def_polled = true;
         if (h->sf_def_inflight) { HIPCHK(h, hipEventSynchronize(h->ev_rs_done)); h->sf_def_inflight = false; }
         if (h->sf_def_unfetched) memcpy(stats, h->h_sf_stats, sizeof(int32_t) * 4 * h->cfg.n_ensembles);
         else memset(stats, 0, sizeof(int32_t) * 4 * h->cfg.n_ensembles);
         h->sf_def_unfetched = false;
         return DABPHY_OK;
     }
+    if (!h->last_frames || !h->last_desc) return DABPHY_ERR_INVALID;
     if (h->sf_stats_ready && h->h_sf_stats_valid) {      // the filter rode in dabphy_process and its totals came back with the batch
         h->sf_stats_ready = false; h->h_sf_stats_valid = false;
         memcpy(stats, h->h_sf_stats, sizeof(int32_t) * 4 * h->cfg.n_ensembles);
