@@ -1814,7 +1814,53 @@ def door_dropout(d_factory, F=4):
         d.close()
 
 
+def door_kinds_change(d_factory, F=3, at=3):
+    """audio kinds change while a pass waits: the last position of both lists becomes MP2 in front of call `at`.  The waiting pass of batch
+    at - 1 runs with the kinds its batch was decoded with (all three services); from batch `at` on the DAB+ filter leaves the position out"""
+    from welle_io_amd import capi
+    x, subchs, o = deferred_stream(16)
+    d = open_deferred(d_factory, x, subchs, 2, F, pipeline_sync=1)
+    try:
+        tracks = fresh_tracks(subchs, o, 2)
+        cum = {}
+
+        def tracks_of(k, info):
+            cum[k] = tracks[0][-1].tot.copy()       # (the oracle's filter of the position that leaves, up to the end of batch k - 1)
+            return tracks if k < at else [t[:-1] + [None] for t in tracks]
+
+        def change(d, want, got):
+            for b in range(2):
+                d.set_audio_kinds_ensemble(b, [capi.AUDIO_DABPLUS] * (len(subchs) - 1) + [capi.AUDIO_MP2])
+        want, got, infos = drive_deferred(d, [F] * 6, tracks_of, before={at: change})
+        stream_conditions(want, infos)
+        # the oracle counts something for the position that leaves in batch at - 1: a waiting pass that ran with the new run lists left it
+        # out and could not return that batch's totals
+        assert (cum[at] - cum[at - 1]).any(), (cum[at - 1].tolist(), cum[at].tolist())
+        assert_deferred_sequence(d, want, got)
+    finally:
+        d.close()
+
+
+def door_left_unfetched(d_factory, F=2, at=4):
+    """mode 2 is left for manual mode (0) with the last batch's totals not fetched: they are parked, and the next process() makes them
+    stale -- the fetch behind it runs the filter over ITS batch"""
+    x, subchs, o = deferred_stream(16)
+    d = open_deferred(d_factory, x, subchs, 2, F, pipeline_sync=1)
+    try:
+        tracks = fresh_tracks(subchs, o, 2)
+        want, got, infos = drive_deferred(d, [F] * 7, lambda k, info: tracks, before={at: lambda d, w, g: d.set_auto_superframes(0)})
+        stream_conditions(want, infos, invalid=False)
+        assert not np.array_equal(want[at - 1], want[at]), "the parked totals equal the next batch's: %s" % want[at].tolist()
+        expect = [np.zeros_like(want[0])] + want[:at - 1] + want[at:]         # (batch at - 1: filtered when the mode was left, never fetched)
+        for k in range(len(want)):
+            assert np.array_equal(got[k], expect[k]), "fetch behind call %d: %s, expected %s" % (k, got[k].tolist(), expect[k].tolist())
+    finally:
+        d.close()
+
+
 DEFERRED_SIDE_DOORS = {
+    "kinds_change": door_kinds_change,
+    "left_unfetched": door_left_unfetched,
     "growing_n_frames": door_growing_frames,
     "service_changes": door_service_changes,
     "mode_switches": door_mode_switches,

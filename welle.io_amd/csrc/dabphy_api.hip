@@ -416,7 +416,7 @@ int apply_subchannels(dabphy_handle* h)
     const std::vector<std::vector<dabphy_handle::PairRef>> old_where = h->where;
     const std::vector<std::vector<dabphy_subchannel>> old_lists = h->subch_e;
     h->fplan.valid = false; h->fplan.launched = false; h->buf_gen++;          // the plan names the classes' buffers
-    h->last_frames = 0; h->last_desc = nullptr; h->sf_stats_ready = false; h->h_sf_stats_valid = false;   // the class outputs of the last batch go with the classes
+    h->last_frames = 0; h->last_desc = nullptr; sf_outputs_go(h);   // the class outputs of the last batch go with the classes
     h->mp2_done = false;
     h->subch_e = h->subch_next;
     h->subch_dirty = false;

@@ -191,7 +191,7 @@ struct dabphy_handle {
     FrameDesc* h_desc = nullptr;      // host copy of the last batch's frame descriptors (page-locked, [B][max_frames])
     float* h_snr = nullptr;
     uint8_t *h_fib = nullptr, *h_ok = nullptr;   // ... of its FIBs [B][F][12][32] and CRC flags [B][F][12]: they cross PCIe inside the step, beside the decoder
-    int32_t* h_sf_stats = nullptr; bool h_sf_stats_valid = false;   // ... of the superframe totals when the filter rode in dabphy_process
+    int32_t* h_sf_stats = nullptr;    // ... of the superframe totals when the filter rode in dabphy_process (sf.totals)
     // stage timing (HIP events on the handle's stream, recorded when profiling is on)
     enum { ST_SYNC = 0, ST_DEMOD, ST_SNR, ST_FIC, ST_MSC_GATHER, ST_MSC_VITERBI, ST_RS, ST_COUNT };
     bool profiling = false;
@@ -202,24 +202,38 @@ struct dabphy_handle {
     // TII (RadioReceiverOptions::decodeTII): constants, per-batch scratch, per-ensemble sums that live across batches
     bool tii_on = false; bool tii_ran = false;
     bool track_slevel = false;        // dabphy_set_track_slevel: sLevel follows every tracked frame instead of catching up at a loss of lock
-    // dabphy_set_auto_superframes(2): the filter pass of batch k runs beside batch k + 1's FFT stage, on a stream of its own
-    //   state of batch k's pass      pending  inflight  unfetched   set by
-    //   decoded, pass not queued        1        0         -        dabphy_process(k), at its end (sf_def_desc / sf_def_frames name the batch)
-    //   queued on rs_stream             0        1         1        launch_deferred_superframes: dabphy_process(k + 1), a flush, a second fetch
-    //   waited for                      0        0         1        the end of dabphy_process(k + 1); hipEventSynchronize in a flush or a fetch
-    //   totals handed to the caller     0        0         0        dabphy_superframes_stats
-    //   polled: a fetch has been made since the last dabphy_process -- the next one runs a pending pass at once (the end of a stream).
-    //   flush (run now, wait): another sub-channel list or audio kinds, another n_frames, leaving the mode -- which parks unfetched totals
-    //   in h_sf_stats for the next fetch (sf_stats_ready + h_sf_stats_valid) so that the new mode does not filter the batch again.
-    //   dabphy_reset clears all of it.
-    bool sf_deferred = false, sf_def_pending = false, sf_def_unfetched = false, sf_def_inflight = false;
-    bool sf_def_polled = false;             // dabphy_superframes_stats has been called since the last dabphy_process (the next call runs the pending pass)
-    const FrameDesc* sf_def_desc = nullptr; uint32_t sf_def_frames = 0;
-    hipStream_t rs_stream = nullptr; hipEvent_t ev_rs_done = nullptr;
-    bool sf_auto = false, sf_stats_ready = false;   // dabphy_set_auto_superframes: the all-sub-channel filter rides in dabphy_process's submission
+    // dabphy_set_auto_superframes: the all-sub-channel DAB+ filter as a pass of dabphy_process -- of batch k at the end of dabphy_process(k) (mode
+    // 1), or in dabphy_process(k + 1) beside that batch's FFT stage (mode 2).  Only the steps sf_* below (dabphy_superframes.hip) touch this.
+    //   batch k's pass, mode 2           waiting   totals      set by
+    //   decoded, pass not queued         batch k   (k - 1's)   sf_batch_decoded: the end of dabphy_process(k)
+    //   queued on the auxiliary stream   none      IN_FLIGHT   sf_launch_waiting: dabphy_process(k + 1), sf_flush, a second fetch
+    //   waited for                       -         LANDED      sf_batch_decoded, sf_flush or a fetch (mode 1: sf_inline_pass, final with the batch)
+    //   totals handed to the caller      -         EMPTY       dabphy_superframes_stats
+    //   Leaving mode 2 flushes and parks the totals as LANDED (zeros if they have been fetched): the new mode does not filter the batch again.
+    //   Outside mode 2 no batch waits and no pass is in flight.  dabphy_reset drops a waiting batch and mode 2's totals.
+    struct SfPass {
+        enum Mode { OFF, INLINE, DEFERRED } mode = OFF;              // dabphy_set_auto_superframes(0 / 1 / 2)
+        const FrameDesc* desc = nullptr; uint32_t frames = 0;        // the batch that waits for its pass (desc == nullptr: none); `frames` stays the depth of the pass queued last
+        enum Totals { EMPTY, IN_FLIGHT, LANDED } totals = EMPTY;     // of the pass queued last: LANDED = in h_sf_stats, not fetched yet
+        bool polled = false;                                         // a fetch has been made since the last dabphy_process: the next one runs the waiting pass at once (the end of a stream)
+        hipEvent_t done = nullptr;                                   // behind the deferred pass on the auxiliary stream (created with the first one)
+    } sf;
     DevBuf tii_rot, tii_rank, tii_pat, tii_err, tii_likely, tii_state, tii_events, tii_nev, tii_ovf;
     uint32_t tii_max_events = 0;
 };
+
+extern "C" {       // the steps of the superframe filter's pass (dabphy_superframes.hip), one per transition of the table at dabphy_handle::SfPass
+DABPHY_INTERNAL bool sf_pass_on(const dabphy_handle* h);                     // mode 1 or 2: dabphy_process reserves the filter's buffers
+DABPHY_INTERNAL bool sf_windows_carried(const dabphy_handle* h);             // exact batch mode snapshots the filter's windows (for_each_carried)
+DABPHY_INTERNAL int sf_flush(dabphy_handle* h);                              // audio kinds are about to change: the waiting pass runs now and is waited for
+DABPHY_INTERNAL int sf_batch_begins(dabphy_handle* h, uint32_t n_frames);    // ... or the classes, or the batch depth
+DABPHY_INTERNAL int sf_launch_waiting(dabphy_handle* h);                     // the previous batch's pass, on the auxiliary stream
+DABPHY_INTERNAL int sf_wait_for_pass(dabphy_handle* h, hipStream_t st);      // `st` waits for a pass in flight
+DABPHY_INTERNAL void sf_outputs_go(dabphy_handle* h);                        // a new decoder launch or a class rebuild: inline totals are no longer the last batch's
+DABPHY_INTERNAL int sf_inline_pass(dabphy_handle* h);                        // mode 1: this batch's pass, behind its decoders
+DABPHY_INTERNAL void sf_batch_decoded(dabphy_handle* h, const FrameDesc* desc, uint32_t n_frames);
+DABPHY_INTERNAL int sf_stream_reset(dabphy_handle* h);                       // dabphy_reset
+}
 
 namespace dabphy {
 
@@ -326,7 +340,7 @@ template <typename Fn> int for_each_carried(dabphy_handle* h, bool every, Fn fn)
     if ((r = fn((void*)h->d_dec, h->snap_dec, sizeof(DecState) * h->cfg.n_ensembles))) return r;
     if ((r = fn(h->tii_state.p, h->snap_tii, h->tii_state.cap))) return r;
     // (deferred filter: this batch's pass has not run when the batch is decoded again, nothing to put back)
-    if (every || !h->sf_deferred) for (auto& cls : h->classes) if ((r = fn(cls.sf_state.p, cls.sf_snap, cls.sf_state.cap))) return r;
+    if (every || sf_windows_carried(h)) for (auto& cls : h->classes) if ((r = fn(cls.sf_state.p, cls.sf_snap, cls.sf_state.cap))) return r;
     if (every || h->mp2_auto) for (auto& cls : h->classes) if ((every || cls.n_mp2) && (r = fn(cls.mp2_state.p, cls.mp2_snap, cls.mp2_state.cap))) return r;
     return 0;
 }
@@ -376,16 +390,12 @@ DABPHY_INTERNAL void launch_serial_chain(dabphy_handle* h, SyncArgs sa);
 DABPHY_INTERNAL int queue_chain(dabphy_handle* h, int sel, uint32_t F);
 DABPHY_INTERNAL int resolve_chain(dabphy_handle* h, int sel);
 DABPHY_INTERNAL int prepare_superframes(dabphy_handle* h, uint32_t F);       // dabphy_superframes.hip
-DABPHY_INTERNAL int run_superframes(dabphy_handle* h, const std::vector<dabphy::SfSel>& sel, int32_t* stats, hipStream_t st = nullptr, const FrameDesc* desc = nullptr, uint32_t n_frames = 0);
 DABPHY_INTERNAL int apply_subchannels(dabphy_handle* h);                                          // dabphy_api.hip
 DABPHY_INTERNAL int apply_audio_kinds(dabphy_handle* h);                                          // dabphy_mp2.hip
 DABPHY_INTERNAL int prepare_mp2(dabphy_handle* h, uint32_t F);
 DABPHY_INTERNAL int launch_mp2_pass(dabphy_handle* h, uint32_t F);
 DABPHY_INTERNAL size_t mp2_stride();
 DABPHY_INTERNAL int upload_pairs(dabphy_handle* h, dabphy_handle::MscClass& cls);
-DABPHY_INTERNAL int launch_superframe_stats(dabphy_handle* h, hipStream_t st = nullptr, const FrameDesc* desc = nullptr, uint32_t n_frames = 0);
-DABPHY_INTERNAL int launch_deferred_superframes(dabphy_handle* h);       // dabphy_set_auto_superframes(2): the pending pass of the previous batch, on rs_stream
-DABPHY_INTERNAL int flush_deferred_superframes(dabphy_handle* h);        // ... now, and wait for it
 DABPHY_INTERNAL int fused_class_tables(dabphy_handle* h, const dabphy_protection& prot, bool fic, DevBuf (&steps)[FUSED_VARIANTS], int (&n_windows)[FUSED_VARIANTS]);   // dabphy_fused.hip
 DABPHY_INTERNAL int fused_plan(dabphy_handle* h, uint32_t F, bool want_fic);
 DABPHY_INTERNAL bool sp_single_ok(const dabphy_handle* h, uint64_t n_cw, int nsteps);

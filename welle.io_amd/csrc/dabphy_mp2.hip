@@ -28,8 +28,7 @@ int apply_audio_kinds(dabphy_handle* h)
     }
     int r;
     if (device_work) {
-        // nothing queued may still read the run lists (the deferred DAB+ pass of the last batch: run now, with the kinds it was decoded with)
-        if ((h->sf_def_pending || h->sf_def_inflight) && (r = flush_deferred_superframes(h))) return r;
+        if ((r = sf_flush(h))) return r;      // nothing queued may still read the run lists (the deferred DAB+ pass of the last batch: run now, with the kinds it was decoded with)
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     const size_t stride = mp2_stride();

@@ -96,7 +96,7 @@ static int reserve_batch(dabphy_handle* h, const Batch& b)
         const size_t n_groups = ((size_t)4 * F * cls.pairs.size() + 63) / 64;
         if ((r = ensure(h, cls.out, n_groups * 64 * (cls.prot.nbits / 8)))) return r;
     }
-    if (h->sf_auto && (r = prepare_superframes(h, F))) return r;
+    if (sf_pass_on(h) && (r = prepare_superframes(h, F))) return r;
     if (h->mp2_auto && (r = prepare_mp2(h, F))) return r;
     // (the replay of exact batch mode decodes one frame's FIC at a time, state-parallel when 4 B code words are few: its buffers now)
     if (replay_armed(h, F) && sp_single_ok(h, (uint64_t)B * 4, fic.nsteps) && (r = sp_single_reserve(h, (uint64_t)B * 4, fic.nsteps))) return r;
@@ -113,7 +113,7 @@ static int reserve_batch(dabphy_handle* h, const Batch& b)
         if ((r = ensure(h, h->fsym, fic_groups * fic.nsteps * 64 * sizeof(uint32_t)))) return r;
         if ((r = ensure(h, h->fdec, fic_groups * fic.nsteps * 64 * sizeof(uint2)))) return r;
     }
-    if (h->sf_auto && (r = ensure(h, h->sf_stats, sizeof(int32_t) * 4 * B))) return r;
+    if (sf_pass_on(h) && (r = ensure(h, h->sf_stats, sizeof(int32_t) * 4 * B))) return r;
     if (h->exact_batch) {       // a snapshot for everything a batch carries (dabphy_internal.h: for_each_carried)
         const auto reserve = [&](void*, DevBuf& snap, size_t bytes) { return ensure(h, snap, bytes); };
         for (int k = 0; k < dabphy_handle::N_DESC; k++) if ((r = for_each_carried_sync(h, k, reserve))) return r;
@@ -210,10 +210,7 @@ static int queue_next_chains(dabphy_handle* h, const Batch& b)
 {
     int r;
     if (h->cfg.pipeline_sync != 2) HIPCHK(h, hipStreamWaitEvent(h->sync_stream, h->ev_chain_gate, 0));
-    // (dabphy_set_auto_superframes(2): TWO batches ahead -- only then: N_DESC = 3 --, the chain queued here writes the descriptor buffer of
-    // the PREVIOUS batch, whose filter pass -- launched earlier in this call, decode_batch -- reads valid / frame_no from it: the chain
-    // waits for that pass.  One batch ahead the chain writes another buffer and waits for nothing)
-    if (b.depth == 2 && h->sf_def_inflight && h->ahead < 1 + b.depth) HIPCHK(h, hipStreamWaitEvent(h->sync_stream, h->ev_rs_done, 0));
+    if (b.depth == 2 && h->ahead < 1 + b.depth && (r = sf_wait_for_pass(h, h->sync_stream))) return r;
     for (; h->ahead < 1 + b.depth; h->ahead++) if ((r = queue_chain(h, (b.cur + h->ahead) % dabphy_handle::N_DESC, b.F))) return r;
     return 0;
 }
@@ -265,8 +262,7 @@ static int queue_aux_work(dabphy_handle* h, const Batch& b)
 // MSC (+ FIC): every class the plan holds in ONE launch; the stage events bracket all of it
 static int launch_fused(dabphy_handle* h, const Batch& b)
 {
-    h->last_frames = b.F;
-    h->sf_stats_ready = false; h->h_sf_stats_valid = false;
+    h->last_frames = b.F; sf_outputs_go(h);
     if (h->fplan.args.n_work <= 0) return 0;
     FusedArgs fa = h->fplan.args; fa.desc = b.d_desc;
     h->fplan.args = fa; h->fplan.launched = true;
@@ -337,9 +333,7 @@ static int decode_batch(dabphy_handle* h, Batch& b, const bool replay)
     // (cfg.sync_early: in front of the decoder (0, the default: neutral on the headline, 0.2 ms on a batch of drifting ensembles, whose
     // window searches run one after the other in the find chain -- latency-bound work for one work-group per ensemble that belongs beside the
     // decoder); behind it (1); in front only while the last pass met ensembles whose window moves (2); 3: an experiment, see below)
-    // dabphy_set_auto_superframes(2), two batches ahead: the PREVIOUS batch's filter pass in front of the next chains, one of which reuses
-    // the descriptors it reads and has to wait for it (queue_next_chains); on the other schedules it keeps its place below
-    if (!replay && b.depth == 2 && h->sf_auto && h->sf_deferred && (r = launch_deferred_superframes(h))) return r;
+    if (!replay && b.depth == 2 && (r = sf_launch_waiting(h))) return r;
     const bool early = h->chain_early || (h->cfg.pipeline_sync != 2 && (h->cfg.sync_early == 0 || h->cfg.sync_early == 3 || (h->cfg.sync_early == 2 && h->drift_seen)));
     if (!replay && b.depth && early) {
         // the next batch's synchroniser is handed to the device BEFORE this batch's decoder (whose persistent waves would otherwise hold
@@ -351,22 +345,15 @@ static int decode_batch(dabphy_handle* h, Batch& b, const bool replay)
         // proper, ~0.8 ms of throughput work that then has the device to itself; the find chain's rounds run beside the decoder)
         if (h->cfg.sync_early == 3 && h->wide_front_recorded) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_wide_front, 0));
     }
-    // dabphy_set_auto_superframes(2): the PREVIOUS batch's superframe filter pass, beside this batch's FFT stage (nothing left to launch when
-    // it went in front of the chains above); this batch's decoders wait for it on the device before they overwrite the class outputs it reads
-    if (!replay && h->sf_auto && h->sf_deferred && (r = launch_deferred_superframes(h))) return r;
-    if (h->sf_def_inflight) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_rs_done, 0));
+    if (!replay && (r = sf_launch_waiting(h))) return r;       // (dabphy_set_auto_superframes(2): the PREVIOUS batch's filter pass)
+    if ((r = sf_wait_for_pass(h, h->stream))) return r;
     if ((r = queue_aux_work(h, b))) return r;
     // pairs selected since the last batch learn the CIF count they start at (their time de-interleaver fills from here, dab-audio.cpp:146-149)
     for (auto& cls : h->classes) if (cls.cif0_pending) launch_pair_cif0(cls.pair_tab.as<MscPair>(), (int)cls.pairs.size(), b.d_desc, (int)b.F, h->stream);
     if ((r = launch_fused(h, b))) return r;
     if ((r = queue_fic_verdict(h, b, replay))) return r;
     if ((r = decode_unfused_classes(h, b))) return r;
-    if (h->sf_auto && !h->sf_deferred) {
-        if ((r = launch_superframe_stats(h))) return r;
-        h->sf_stats_ready = true;
-        launch_copy_out(h->sf_stats.p, h->h_sf_stats, sizeof(int32_t) * 4 * b.B, h->stream);
-        h->h_sf_stats_valid = true;
-    }
+    if ((r = sf_inline_pass(h))) return r;
     if (h->mp2_auto && (r = launch_mp2_pass(h, b.F))) return r;
     return DABPHY_OK;
 }
@@ -431,9 +418,7 @@ int dabphy_process(dabphy_handle* h, uint32_t n_frames)
     const uint32_t F = b.F = n_frames;
     b.B = h->cfg.n_ensembles; b.ring_frames = (int)h->cfg.max_frames + 5; b.ens_stride = soft_ens_stride(h);
     int r;
-    // the deferred filter pass of the last batch belongs to the classes that are about to be rebuilt, and to class outputs of its own
-    // depth: another n_frames may grow them (reserve_batch: grow-only scratch, contents not kept) -- the pass runs now, and is waited for
-    if ((h->subch_dirty || n_frames != h->sf_def_frames) && (h->sf_def_pending || h->sf_def_inflight) && (r = flush_deferred_superframes(h))) return r;
+    if ((r = sf_batch_begins(h, n_frames))) return r;        // (a deferred filter pass of the last batch that cannot wait any longer)
     if ((r = apply_subchannels(h))) return r;                // per-ensemble sub-channel changes since the last batch (dabphy_set_subchannels_ensemble)
     if ((r = apply_audio_kinds(h))) return r;                // ... and audio kinds (dabphy_set_audio_kinds_ensemble)
     if ((r = reserve_batch(h, b))) return r;
@@ -471,11 +456,7 @@ int dabphy_process(dabphy_handle* h, uint32_t n_frames)
     tick(h, b, 4);
     if (replay_armed(h, F) && *h->h_any_eff && (r = replay_batch(h, b))) return r;
 
-    if (h->sf_auto && h->sf_deferred) {
-        // (the main stream has waited for the previous batch's pass: its totals are in host memory; this batch's pass is the next call's)
-        h->sf_def_inflight = false;
-        h->sf_def_pending = true; h->sf_def_desc = b.d_desc; h->sf_def_frames = F; h->sf_def_polled = false;
-    }
+    sf_batch_decoded(h, b.d_desc, F);
     // the host's mirror of the pair tables follows what k_pair_cif0 wrote (same rule, from the host's copy of the descriptors)
     for (auto& cls : h->classes) if (cls.cif0_pending) {
         for (MscPair& p : cls.pairs) if (p.cif0 < 0) p.cif0 = 4 * h->h_desc[(size_t)p.ens * F].frame_no;

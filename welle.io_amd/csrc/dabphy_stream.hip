@@ -134,8 +134,7 @@ int dabphy_reset(dabphy_handle* h)
     int r = reset_synchroniser(h, true); if (r) return r;
     h->desc_sel = 0; h->n_wide_passes = h->n_wide_fallbacks = 0; h->n_replayed_batches = 0;
     h->last_frames = 0; h->last_desc = nullptr;
-    if (h->rs_stream) HIPCHK(h, hipStreamSynchronize(h->rs_stream));
-    h->sf_def_pending = h->sf_def_unfetched = h->sf_def_inflight = h->sf_def_polled = false;      // (a deferred filter pass of the stream that ends here is dropped with it)
+    if ((r = sf_stream_reset(h))) return r;
     // everything the decoders carry from batch to batch starts from zero (RadioReceiver::restart_decoder; a new OFDMProcessor owns a new
     // TIIDecoder); the pair tables and their cif0 below are reset too but are no snapshot of exact batch mode, so they stand apart
     r = for_each_carried(h, true, [&](void* live, DevBuf&, size_t bytes) -> int { if (live) HIPCHK(h, hipMemsetAsync(live, 0, bytes, h->stream)); return 0; });

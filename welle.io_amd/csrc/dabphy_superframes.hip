@@ -129,15 +129,12 @@ int dabphy_rs_decode_msc(dabphy_handle* h, int32_t subch_index, const int32_t* f
 // classes of a bucket (kernel LDS size) go in ONE launch each of the wide pass, the verdict and the serial walk; their argument blocks
 // travel through a page-locked staging area that the caller must not reuse before the stream has been synchronised (every caller
 // synchronises before it returns, dabphy_process at its end).
-int run_superframes(dabphy_handle* h, const std::vector<SfSel>& sel, int32_t* stats, hipStream_t st, const FrameDesc* desc, uint32_t n_frames)
+static int run_superframes(dabphy_handle* h, const std::vector<SfSel>& sel, int32_t* stats, hipStream_t st, const FrameDesc* desc, uint32_t F)
 {
-    const uint32_t F = n_frames ? n_frames : h->last_frames;        // (a deferred pass names the batch it belongs to: the handle has moved on)
-    if (!desc) desc = h->last_desc;
-    const int n_cif = (int)(4 * F), n_slots = n_cif / 5 + 1;
+    const int n_cif = (int)(4 * F), n_slots = n_cif / 5 + 1;        // (desc, F: a deferred pass names the batch it belongs to, the handle has moved on)
     int r;
     if ((r = prepare_superframes(h, F))) return r;
     if (!h->sf_batch.p) return 0;                                        // no DAB+-rate class at all
-    if (!st) st = h->stream;
     // staging layout per bucket: [SF_BATCH_CLASSES argument blocks][SF_BATCH_CLASSES + 1 first blocks]
     uint8_t* const hs = reinterpret_cast<uint8_t*>(h->h_sf_batch);
     uint8_t* const ds = h->sf_batch.as<uint8_t>();
@@ -197,7 +194,7 @@ int superframes_of(dabphy_handle* h, const std::vector<dabphy_handle::PairRef>& 
         used += mine.size(); mine_of.push_back(std::move(mine));
     }
     HIPCHK(h, hipMemcpyAsync(h->sf_run.p, run.data(), used * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    if ((r = run_superframes(h, sel, nullptr, h->stream))) return r;
+    if ((r = run_superframes(h, sel, nullptr, h->stream, h->last_desc, F))) return r;
     for (size_t s = 0; s < sel.size(); s++) {
         const auto& cls = h->classes[sel[s].cls];
         for (size_t i : mine_of[s]) {
@@ -242,14 +239,15 @@ int dabphy_superframes_ensemble(dabphy_handle* h, uint32_t ensemble, uint32_t su
     return superframes_of(h, rows, cls.prot.nbits / 8, events, n_events, sf);
 }
 
-// SuperframeFilter over every DAB+ sub-channel of every ensemble: the classes of a bucket in one launch each on the main stream, totals into sf_stats
-int launch_superframe_stats(dabphy_handle* h, hipStream_t st, const FrameDesc* desc, uint32_t n_frames)
+namespace {
+using SfPass = dabphy_handle::SfPass;
+static size_t sf_totals_bytes(const dabphy_handle* h) { return sizeof(int32_t) * 4 * h->cfg.n_ensembles; }
+// SuperframeFilter over every DAB+ sub-channel of every ensemble, totals into sf_stats: over the last batch on the main stream, or -- deferred -- over the batch that waits in h->sf on the auxiliary stream
+static int launch_superframe_stats(dabphy_handle* h, bool deferred = false)
 {
-    const uint32_t B = h->cfg.n_ensembles;
-    if (!st) st = h->stream;
-    int r;
-    if ((r = ensure(h, h->sf_stats, sizeof(int32_t) * 4 * B))) return r;
-    HIPCHK(h, hipMemsetAsync(h->sf_stats.p, 0, sizeof(int32_t) * 4 * B, st));
+    hipStream_t st = deferred ? h->aux_stream : h->stream; int r;
+    if ((r = ensure(h, h->sf_stats, sf_totals_bytes(h)))) return r;
+    HIPCHK(h, hipMemsetAsync(h->sf_stats.p, 0, sf_totals_bytes(h), st));
     std::vector<SfSel> sel;
     for (size_t ci = 0; ci < h->classes.size(); ci++) {
         const auto& c = h->classes[ci];
@@ -259,39 +257,60 @@ int launch_superframe_stats(dabphy_handle* h, hipStream_t st, const FrameDesc* d
     }
     if (sel.empty()) return 0;
     if (h->profiling) { hipError_t e = hipEventRecord(h->ev_beg[dabphy_handle::ST_RS], st); (void)e; }
-    if ((r = run_superframes(h, sel, h->sf_stats.as<int32_t>(), st, desc, n_frames))) return r;
+    if ((r = run_superframes(h, sel, h->sf_stats.as<int32_t>(), st, deferred ? h->sf.desc : h->last_desc, deferred ? h->sf.frames : h->last_frames))) return r;
     if (h->profiling) { hipError_t e = hipEventRecord(h->ev_end[dabphy_handle::ST_RS], st); (void)e; h->ev_used[dabphy_handle::ST_RS] = true; }
     return 0;
 }
+// the host waits for a pass in flight: its totals are in h_sf_stats
+static int land_totals(dabphy_handle* h) { if (h->sf.totals == SfPass::IN_FLIGHT) { HIPCHK(h, hipEventSynchronize(h->sf.done)); h->sf.totals = SfPass::LANDED; } return DABPHY_OK; }
+}
 
-// dabphy_set_auto_superframes(2).  The filter pass of a batch needs nothing but the batch's class outputs and descriptors and the
-// windows it carries; nothing of the NEXT batch needs its results before that batch's decoders overwrite the class outputs.  So the pass of
-// batch k is queued by dabphy_process(k + 1), behind that batch's demod launch, on a stream of its own: it runs beside the FFT stage
-// instead of in the step's tail, and the decoders of batch k + 1 wait for it on the device (it is long done by then).
-int launch_deferred_superframes(dabphy_handle* h)
+// ---- the filter as a pass of dabphy_process (dabphy_set_auto_superframes).  Every access to h->sf is below; dabphy_internal.h has the table.
+bool sf_pass_on(const dabphy_handle* h) { return h->sf.mode != SfPass::OFF; }
+bool sf_windows_carried(const dabphy_handle* h) { return h->sf.mode != SfPass::DEFERRED; }     // (deferred: this batch's pass has not run when exact batch mode decodes the batch again, nothing to put back)
+
+// Mode 2: the pass of batch k is queued by dabphy_process(k + 1) behind that batch's demod launch, and runs beside the FFT
+// stage instead of in the step's tail.  decode_batch calls this twice: two batches ahead in front of the next chains, one of which reuses
+// the descriptors the pass reads and has to wait for it; on every schedule in front of the decoders, where nothing is left to launch
+// when it went in front of the chains.  (On the AUXILIARY stream, idle until this batch's demod kernel has finished: a stream of its own
+// would be the handle's eighth, the runtime multiplexes them onto four hardware queues, and the first version ran behind the demod kernel)
+int sf_launch_waiting(dabphy_handle* h)
 {
-    if (!h->sf_def_pending) return DABPHY_OK;
-    const uint32_t B = h->cfg.n_ensembles;
-    // (on the AUXILIARY stream, which is idle until this batch's demod kernel has finished: a stream of its own would be the handle's
-    // eighth, and the runtime multiplexes streams onto four hardware queues -- the first version shared one with the main stream and ran
-    // behind the demod kernel instead of beside it: profiles/r06_step_variants.txt)
-    if (!h->rs_stream) {
-        h->rs_stream = h->aux_stream;
-        const int rc = new_event(h, &h->ev_rs_done);
-        if (rc) return rc;
-    }
-    int r;
-    if ((r = launch_superframe_stats(h, h->rs_stream, h->sf_def_desc, h->sf_def_frames))) return r;
-    launch_copy_out(h->sf_stats.p, h->h_sf_stats, sizeof(int32_t) * 4 * B, h->rs_stream);
-    HIPCHK(h, hipEventRecord(h->ev_rs_done, h->rs_stream));
-    h->sf_def_pending = false; h->sf_def_inflight = true; h->sf_def_unfetched = true;
+    SfPass& p = h->sf; int r;
+    if (!p.desc) return DABPHY_OK;
+    if (!p.done && (r = new_event(h, &p.done))) return r;
+    if ((r = launch_superframe_stats(h, true))) return r;
+    launch_copy_out(h->sf_stats.p, h->h_sf_stats, sf_totals_bytes(h), h->aux_stream);
+    HIPCHK(h, hipEventRecord(p.done, h->aux_stream));
+    p.desc = nullptr; p.totals = SfPass::IN_FLIGHT;
     return DABPHY_OK;
 }
-int flush_deferred_superframes(dabphy_handle* h)
+// The main stream waits before this batch's decoders overwrite the class outputs the pass reads.  The synchroniser's stream waits TWO batches ahead -- only then:
+// N_DESC = 3 --, when the chain queued next writes the descriptor buffer of the PREVIOUS batch, whose pass reads valid / frame_no from it
+int sf_wait_for_pass(dabphy_handle* h, hipStream_t st) { if (h->sf.totals == SfPass::IN_FLIGHT) HIPCHK(h, hipStreamWaitEvent(st, h->sf.done, 0)); return DABPHY_OK; }
+// The waiting pass now, and the host waits for it: what it reads is about to change -- audio kinds; the classes, which a batch rebuilds; class outputs of its own depth, which another n_frames may grow (reserve_batch: contents not kept)
+int sf_flush(dabphy_handle* h) { const int r = sf_launch_waiting(h); return r ? r : land_totals(h); }
+int sf_batch_begins(dabphy_handle* h, uint32_t n_frames) { return h->subch_dirty || n_frames != h->sf.frames ? sf_flush(h) : DABPHY_OK; }
+void sf_outputs_go(dabphy_handle* h) { if (h->sf.mode != SfPass::DEFERRED) h->sf.totals = SfPass::EMPTY; }      // (mode 2's totals are the batch before's: they stay)
+int sf_inline_pass(dabphy_handle* h)
 {
-    int r;
-    if ((r = launch_deferred_superframes(h))) return r;
-    if (h->sf_def_inflight) { HIPCHK(h, hipEventSynchronize(h->ev_rs_done)); h->sf_def_inflight = false; }
+    if (h->sf.mode != SfPass::INLINE) return DABPHY_OK;
+    if (int r = launch_superframe_stats(h)) return r;
+    launch_copy_out(h->sf_stats.p, h->h_sf_stats, sf_totals_bytes(h), h->stream); h->sf.totals = SfPass::LANDED;       // (once dabphy_process has returned: it ends with the main stream drained)
+    return DABPHY_OK;
+}
+void sf_batch_decoded(dabphy_handle* h, const FrameDesc* desc, uint32_t n_frames)
+{
+    SfPass& p = h->sf;
+    if (p.mode != SfPass::DEFERRED) return;
+    if (p.totals == SfPass::IN_FLIGHT) p.totals = SfPass::LANDED;       // (the main stream has waited for the previous batch's pass: its totals are in host memory)
+    p.desc = desc; p.frames = n_frames; p.polled = false;               // this batch's pass is the next call's
+}
+int sf_stream_reset(dabphy_handle* h)       // a deferred pass of the stream that ends here is dropped with it (inline totals stay: no fetch reaches them before the next launch)
+{
+    SfPass& p = h->sf;
+    if (p.done) HIPCHK(h, hipStreamSynchronize(h->aux_stream));
+    p.desc = nullptr; p.polled = false; if (p.mode == SfPass::DEFERRED) p.totals = SfPass::EMPTY;
     return DABPHY_OK;
 }
 
@@ -299,19 +318,17 @@ int dabphy_set_auto_superframes(dabphy_handle* h, int32_t on)
 {
     DeviceBind dev_(h);
     if (!h) return DABPHY_ERR_INVALID;
-    if (h->sf_deferred && on != 2) {
-        // leaving the deferred mode: nothing stays pending -- the last batch's pass runs now if it has not -- and the last batch is not
-        // filtered a second time by the mode that follows: its totals, unless they have been fetched (then zeros), are what the next
-        // dabphy_superframes_stats returns
-        int r = flush_deferred_superframes(h); if (r) return r;
-        if (h->last_frames && h->h_sf_stats) {
-            if (!h->sf_def_unfetched) memset(h->h_sf_stats, 0, sizeof(int32_t) * 4 * h->cfg.n_ensembles);
-            h->sf_stats_ready = h->h_sf_stats_valid = true;
-        }
-        h->sf_def_unfetched = h->sf_def_polled = false;
-    }
-    h->sf_auto = on != 0;
-    h->sf_deferred = on == 2;
+    SfPass& p = h->sf;
+    const SfPass::Mode mode = on == 2 ? SfPass::DEFERRED : on ? SfPass::INLINE : SfPass::OFF;
+    if (p.mode == SfPass::DEFERRED && mode != p.mode) {
+        // leaving the deferred mode: nothing stays waiting -- the last batch's pass runs now if it has not -- and the mode that follows does not filter
+        // the last batch a second time: its totals, unless they have been fetched (then zeros), are what the next dabphy_superframes_stats returns
+        int r = sf_flush(h); if (r) return r;
+        const bool park = h->last_frames && h->h_sf_stats;
+        if (park && p.totals != SfPass::LANDED) memset(h->h_sf_stats, 0, sf_totals_bytes(h));
+        p.totals = park ? SfPass::LANDED : SfPass::EMPTY; p.polled = false;
+    } else if (mode == SfPass::DEFERRED && mode != p.mode) p.totals = SfPass::EMPTY;     // (inline totals not fetched: mode 2 never returned them, and zeroed them when it was left)
+    p.mode = mode;
     return DABPHY_OK;
 }
 
@@ -319,28 +336,22 @@ int dabphy_superframes_stats(dabphy_handle* h, int32_t* stats)
 {
     DeviceBind dev_(h);
     if (!h || !stats) return DABPHY_ERR_INVALID;
-    int r;
-    if (h->sf_auto && h->sf_deferred) {      // (needs no batch: zeros when nothing is pending or unfetched, as after dabphy_reset)
+    SfPass& p = h->sf; int r;
+    if (p.mode == SfPass::DEFERRED) {      // (needs no batch: zeros when nothing waits or has landed, as after dabphy_reset)
         // the first call after a dabphy_process: the totals of the pass that call queued (the batch BEFORE it), zeros if it queued
-        // none.  One more call without a dabphy_process in between: the pending pass of the last batch runs now (the end of a stream)
-        if (h->sf_def_polled && !h->sf_def_unfetched && h->sf_def_pending) { if ((r = launch_deferred_superframes(h))) return r; }
-        h->sf_def_polled = true;
-        if (h->sf_def_inflight) { HIPCHK(h, hipEventSynchronize(h->ev_rs_done)); h->sf_def_inflight = false; }
-        if (h->sf_def_unfetched) memcpy(stats, h->h_sf_stats, sizeof(int32_t) * 4 * h->cfg.n_ensembles);
-        else memset(stats, 0, sizeof(int32_t) * 4 * h->cfg.n_ensembles);
-        h->sf_def_unfetched = false;
-        return DABPHY_OK;
+        // none.  One more call without a dabphy_process in between: the waiting pass of the last batch runs now (the end of a stream)
+        if (p.polled && p.totals == SfPass::EMPTY && (r = sf_launch_waiting(h))) return r;
+        p.polled = true; if ((r = land_totals(h))) return r;
+    } else if (!h->last_frames || !h->last_desc) return DABPHY_ERR_INVALID;
+    else if (p.totals != SfPass::LANDED) {       // manual mode, or one more fetch of a batch: the filter runs, every time (and feeds the same frames again)
+        if ((r = launch_superframe_stats(h))) return r;
+        HIPCHK(h, hipMemcpyAsync(stats, h->sf_stats.p, sf_totals_bytes(h), hipMemcpyDeviceToHost, h->stream));
+        return sync(h);
     }
-    if (!h->last_frames || !h->last_desc) return DABPHY_ERR_INVALID;
-    if (h->sf_stats_ready && h->h_sf_stats_valid) {      // the filter rode in dabphy_process and its totals came back with the batch
-        h->sf_stats_ready = false; h->h_sf_stats_valid = false;
-        memcpy(stats, h->h_sf_stats, sizeof(int32_t) * 4 * h->cfg.n_ensembles);
-        return DABPHY_OK;
-    }
-    if (!h->sf_stats_ready) { if ((r = launch_superframe_stats(h))) return r; }
-    h->sf_stats_ready = false;                   // one filter pass per batch: a second call would feed the same frames again
-    HIPCHK(h, hipMemcpyAsync(stats, h->sf_stats.p, sizeof(int32_t) * 4 * h->cfg.n_ensembles, hipMemcpyDeviceToHost, h->stream));
-    return sync(h);
+    if (p.totals == SfPass::LANDED) memcpy(stats, h->h_sf_stats, sf_totals_bytes(h));
+    else memset(stats, 0, sf_totals_bytes(h));       // (mode 2 only: no pass was queued)
+    p.totals = SfPass::EMPTY;
+    return DABPHY_OK;
 }
 
 } // extern "C"
