@@ -55,6 +55,12 @@ int dabphy_selftest_pair_exchange(dabphy_handle* h, uint64_t* counts);   /* (als
  * classes (not counting the FIC) that rode in that launch -- the others took the two-kernel path.  Either pointer may be NULL. */
 int dabphy_last_decode_plan(dabphy_handle* h, int32_t* shape, int32_t* fused_classes);
 
+/* Pure host query, no handle and no device: the fused decode's window schedule of a protection class (dabphy_protection_eep / _uep /
+ * _fic) for the kernel's three row counts (batches of >= 64, >= 16, >= 4 CIFs).  n_windows[v] = 16-byte windows of the punctured code
+ * word the schedule walks, 0 = the kernel cannot follow the profile's depuncturing map with that row count (the class then takes the
+ * two-kernel path: same bytes, one more pass through HBM). */
+int dabphy_test_fused_windows(const dabphy_protection* prot, int32_t n_windows[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,94 @@ def check_msc_deconvolve(d, kind, bitrate, a, b, n, seed):
     assert np.array_equal(out, ref)
 
 
+def all_protection_profiles():
+    """every protection profile of EN 300 401 a sub-channel can carry, 304 in all: ("eep", bitrate, profile_b, level) for EEP-A at
+    8..384 kbit/s in steps of 8 and EEP-B at 32..384 in steps of 32, levels 1-4 (240), then ("uep", bitrate, level) for the 64 rows of
+    the short-form table -- read from the ORACLE's copy (itself pinned to the reference's), not from the library under test"""
+    out = []
+    for pb, step in ((0, 8), (1, 32)):
+        for br in range(step, 385, step):
+            for lv in (1, 2, 3, 4):
+                out.append(("eep", br, pb, lv))
+    for i in range(64):
+        br, lv, _ = R.orc_uep_table(i)
+        out.append(("uep", br, lv))
+    return out
+
+
+def profile_family(prof):
+    return "uep" if prof[0] == "uep" else "eep_b" if prof[2] else "eep_a"
+
+
+def profile_name(prof):
+    return "UEP %d kbit/s level %d" % prof[1:] if prof[0] == "uep" else "EEP %d-%s %d kbit/s" % (prof[3], "B" if prof[2] else "A", prof[1])
+
+
+def dev_profile(d, prof):
+    return d.protection_uep(*prof[1:]) if prof[0] == "uep" else d.protection_eep(*prof[1:])
+
+
+def orc_profile(prof):
+    return R.orc_prot_uep(*prof[1:]) if prof[0] == "uep" else R.orc_prot_eep(*prof[1:])
+
+
+# the profiles at which the lane-per-code-word seam (k_lin_gather + k_viterbi) is swept on the CPU execution model: every short-form row,
+# and the long forms at the smallest code words and on either side of 32 767 punctured soft bits (EEP 1-A: 336 | 344 kbit/s)
+LIN_SWEEP_RATES = (8, 16, 32, 336, 344, 384)
+# one full group of 64 code words plus a tail on the device: EEP 1-A on either side of 32 767 soft bits, the longest, and the largest short form
+FULL_GROUP_PROFILES = (("eep", 336, 0, 1), ("eep", 344, 0, 1), ("eep", 384, 0, 1), ("uep", 384, 1))
+
+
+def lin_sweep_profiles():
+    return [p for p in all_protection_profiles() if p[0] == "uep" or p[1] in LIN_SWEEP_RATES]
+
+
+_MSC_PROFILE_CASES = {}     # (profile, n, seed) -> (soft bits, the oracle's bytes), computed once for every handle that asks
+
+
+def msc_profile_case(prof, n, seed):
+    """n code words of uniform random int8 (-128 included: every mapped soft bit then bears on the path metrics) for one profile
+    and the oracle's decoded, de-dispersed bytes; both read-only"""
+    key = (prof, n, seed)
+    if key not in _MSC_PROFILE_CASES:
+        po = orc_profile(prof)
+        rng = np.random.RandomState([seed, {"eep": 0, "uep": 1}[prof[0]]] + [int(v) for v in prof[1:]])
+        s = rng.randint(-128, 128, (n, po.n_in)).astype(np.int8)
+        prbs = R.orc_prbs(po.nbits)
+        ref = np.stack([np.packbits(R.orc_msc_deconvolve(po, s[i]) ^ prbs) for i in range(n)])
+        s.setflags(write=False); ref.setflags(write=False)
+        _MSC_PROFILE_CASES[key] = (s, ref)
+    return _MSC_PROFILE_CASES[key]
+
+
+def check_msc_profiles(d, profiles, n, seed):
+    """dabphy_msc_deconvolve against the oracle on every profile of the list; every failing profile is named with the first byte that
+    differs (a depuncturing map that loses the end of the punctured stream shows as an offset near the end of the code word)"""
+    failed = []
+    for prof in profiles:
+        p = dev_profile(d, prof)
+        s, ref = msc_profile_case(prof, n, seed)
+        if d.protection_input_bits(p) != s.shape[1]:
+            failed.append("%s: consumes %d soft bits, the oracle %d" % (profile_name(prof), d.protection_input_bits(p), s.shape[1]))
+            continue
+        out = d.msc_deconvolve(p, s)
+        if not np.array_equal(out, ref):
+            cw, off = (int(v) for v in np.argwhere(out != ref)[0])
+            failed.append("%s: code word %d of %d differs from byte %d of %d on (%d bytes differ in all)" % (profile_name(prof), cw, n, off, ref.shape[1], int((out != ref).sum())))
+    assert not failed, "%d of %d profiles differ from the oracle:\n  " % (len(failed), len(profiles)) + "\n  ".join(failed)
+
+
+def big_rate_subchannels(case):
+    """ensembles around the longest punctured code words there are, all dabplus=False: 0 = EEP 1-A 384 kbit/s alone at CU 0 (576 CU,
+    36 864 soft bits per CIF); 1 = EEP 1-A 344 kbit/s (516 CU, the first rate past 32 767 soft bits) + EEP 4-A 64 + EEP 3-B 32"""
+    cfgs = [[(1, 384, False, 1)], [(1, 344, False, 1), (2, 64, False, 4), (3, 32, True, 3)]][case]
+    subchs = []; cu = 0
+    for sid, br, pb, lvl in cfgs:
+        sc = synth.SubchannelCfg(sid, cu, br, pb, lvl, dabplus=False); subchs.append(sc); cu += sc.size_cu
+    assert cu <= 864 and subchs[0].size_cu == (576, 516)[case]
+    return subchs
+
+
 def check_fic(d, n_frames, snr_db, seed):
     x = synth.make_stream(n_frames + 1, snr_db=snr_db, seed=seed)
     frames = cut_frames(x, n_frames)
@@ -754,6 +842,17 @@ def check_error_behaviour(d_factory):
         p = d.protection_eep(64, 0, 3)
         bad(lambda: d.set_subchannels([(1, 850, 48, p)]))                         # runs past CU 864
         bad(lambda: d.set_subchannels([(1, 0, 10, p)]))                           # too small for its protection profile
+        # a hand-made profile that keeps the block-count rule but is longer than any of EN 300 401 (9216 bits): refused, so that no index of
+        # a depuncturing map can outgrow its two bytes (dabphy_host.cpp asserts the bound for everything up to that length at compile time)
+        q = d.protection_eep(384, 0, 1); q.nbits = 9248; q.L[0] = 286
+        assert sum(q.L) * 32 == q.nbits and d.protection_input_bits(q) <= 864 * 64
+        for fn in (lambda: d.msc_deconvolve(q, np.zeros((1, d.protection_input_bits(q)), np.int8)), lambda: d.set_subchannels([(1, 0, 864, q)])):
+            try:
+                fn()
+            except DabPhyError as e:
+                assert "status -2" in str(e), str(e)                              # DABPHY_ERR_INVALID
+            else:
+                raise AssertionError("a code word of 9248 bits was accepted")
         x = np.zeros((2, 3 * 196608), np.complex64)
         d.stream_upload(x)
         bad(lambda: d.process(3))                                                 # more frames than max_frames

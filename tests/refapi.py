@@ -158,6 +158,36 @@ def ref_uep(bitrate, level, soft):
     ref().ref_uep_deconvolve(bitrate, level, _p(soft), len(soft), _p(out)); return out
 
 
+REF_SUBCH_SO = os.path.join(ROOT, "oracle", "_ref", "libwelle_ref_subch.so")
+_ref_subch = None
+
+
+def have_ref_subch():
+    return os.path.exists(REF_SUBCH_SO)
+
+
+def ref_subch():
+    """the reference's Subchannel record alone (oracle/ref_subch.cpp): a library of its own beside the harness library"""
+    global _ref_subch
+    if _ref_subch is None:
+        _ref_subch = C.CDLL(REF_SUBCH_SO)
+    return _ref_subch
+
+
+def ref_eep_size_cu(bitrate, profile_b, level):
+    """size in CU of a long-form (EEP) sub-channel as the reference sees it: the one `length` that Subchannel::bitrate() turns into
+    this bit rate and Subchannel::numCU() returns unchanged (dab-constants.cpp:404-477; the reference derives both from `length`)"""
+    lib = ref_subch()
+    hits = [n for n in range(1, 865)
+            if lib.ref_subch_bitrate_of(0, 0, int(profile_b), level, n) == bitrate and lib.ref_subch_num_cu(0, 0, int(profile_b), level, n) == n]
+    assert len(hits) == 1, (bitrate, profile_b, level, hits)
+    return hits[0]
+
+
+def ref_uep_size_cu(table_index):
+    return ref_subch().ref_subch_num_cu(1, table_index, 0, 1, 0)
+
+
 def ref_energy(bits):
     a = np.ascontiguousarray(bits, np.uint8).copy(); ref().ref_energy_dedisperse(_p(a), len(a)); return a
 
@@ -267,13 +297,19 @@ def orc_prot_fic():
     p = OrcProt(); orc().orc_prot_fic(C.byref(p)); return p
 
 
+def orc_uep_table(i):
+    """(bitrate, level, size in CU) of row i of the short-form table"""
+    b = C.c_int(); l = C.c_int(); sz = C.c_int()
+    assert orc().orc_uep_table(i, C.byref(b), C.byref(l), C.byref(sz)) == 0
+    return b.value, l.value, sz.value
+
+
 def orc_uep_row(bitrate, level):
     """(table index, size in CU) of the short-form table row for (bitrate, level)"""
-    b = C.c_int(); l = C.c_int(); sz = C.c_int()
     for i in range(64):
-        assert orc().orc_uep_table(i, C.byref(b), C.byref(l), C.byref(sz)) == 0
-        if b.value == bitrate and l.value == level:
-            return i, sz.value
+        b, l, sz = orc_uep_table(i)
+        if b == bitrate and l == level:
+            return i, sz
     raise ValueError("no UEP row for %d kbit/s level %d" % (bitrate, level))
 
 

@@ -16,6 +16,36 @@ def test_msc_deconvolve(emu, args):
     P.check_msc_deconvolve(emu, *args, n=3, seed=7)
 
 
+def test_msc_deconvolve_every_profile(emu):
+    """all 304 protection profiles through Protection::deconvolve's seam, one code word of random int8 each"""
+    P.check_msc_profiles(emu, P.all_protection_profiles(), n=1, seed=7)
+
+
+def test_msc_deconvolve_profiles_lane_per_code_word(emu):
+    """... and with the lane-per-code-word kernels forced (decode_shape = 1: k_lin_gather + k_viterbi): every short-form row, the long
+    forms at the shortest code words and on either side of 32 767 punctured soft bits"""
+    from welle_io_amd import capi
+    import conftest
+    d = capi.DabPhy(lib_path=conftest.EMU_LIB, decode_shape=1)
+    try:
+        P.check_msc_profiles(d, P.lin_sweep_profiles(), n=1, seed=7)
+    finally:
+        d.close()
+
+
+@pytest.mark.parametrize("shape", [2, 3])
+def test_msc_deconvolve_longest_profiles_state_parallel(emu, shape):
+    """the state-parallel kernels unpack four map entries from two dwords: the profiles with the longest punctured code words (EEP 1-A on
+    either side of 32 767 soft bits and at 384 kbit/s, UEP 384 kbit/s level 1), an odd number of code words"""
+    from welle_io_amd import capi
+    import conftest
+    d = capi.DabPhy(lib_path=conftest.EMU_LIB, decode_shape=shape)
+    try:
+        P.check_msc_profiles(d, P.FULL_GROUP_PROFILES, n=3, seed=7)
+    finally:
+        d.close()
+
+
 def test_fic(emu):
     assert P.check_fic(emu, 3, snr_db=9, seed=4) > 0
 

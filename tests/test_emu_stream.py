@@ -107,6 +107,13 @@ def test_mixed_protection_classes_state_parallel(emu, F, nf):
     P.check_mixed_ensemble(factory_state_parallel, F=F, nf=nf, expect_fused=True)
 
 
+@pytest.mark.parametrize("case", [0, 1])
+def test_longest_punctured_code_words_in_the_stream(emu, case):
+    """EEP 1-A at 384 kbit/s (36 864 soft bits per CIF) / at 344 kbit/s (33 024: the first rate whose punctured code word outgrows a
+    signed 16-bit index) beside two small classes, through the stream's own readers of the depuncturing map: here the state-parallel kernel"""
+    P.check_mixed_ensemble(factory_state_parallel, F=4, nf=11, expect_fused=True, subchs=P.big_rate_subchannels(case))
+
+
 @pytest.mark.parametrize("shape", [1, 2])
 def test_stream_with_either_decoder(emu, shape):
     """the canonical ensemble through both Viterbi kernels explicitly (soft bits, FIBs, MSC bytes of all 18 sub-channels vs the oracle)"""

@@ -109,6 +109,29 @@ def test_seams_with_either_decoder(gpu, shape):
         d.close()
 
 
+@pytest.fixture(scope="module", params=[1, 2, 3])
+def shaped(request, gpu):
+    """a handle with one Viterbi kernel forced: 1 lane per code word (k_lin_gather + k_viterbi), 2 / 3 state-parallel with two / one code
+    words per wavefront"""
+    from welle_io_amd import capi
+    import conftest
+    d = capi.DabPhy(lib_path=conftest.GPU_LIB, decode_shape=request.param)
+    yield d
+    d.close()
+
+
+@pytest.mark.parametrize("family", ["eep_a", "eep_b", "uep"])
+def test_msc_deconvolve_every_profile(shaped, family):
+    """all 304 protection profiles (192 EEP-A, 48 EEP-B, 64 UEP) with each Viterbi kernel, three code words of random int8 each"""
+    P.check_msc_profiles(shaped, [p for p in P.all_protection_profiles() if P.profile_family(p) == family], n=3, seed=7)
+
+
+def test_msc_deconvolve_longest_profiles_full_group(shaped):
+    """a full group of 64 code words and a tail where the punctured code word is longest: EEP 1-A at 336 | 344 kbit/s (either side of
+    32 767 soft bits) and 384, UEP 384 kbit/s level 1"""
+    P.check_msc_profiles(shaped, P.FULL_GROUP_PROFILES, n=67, seed=7)
+
+
 def test_error_behaviour(gpu):
     from welle_io_amd import capi
     import conftest

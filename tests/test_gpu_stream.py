@@ -127,6 +127,16 @@ def test_mixed_protection_classes_state_parallel(gpu, F, nf):
     P.check_mixed_ensemble(factory_state_parallel, F=F, nf=nf, expect_fused=True)
 
 
+@pytest.mark.parametrize("F,nf,shape", [(4, 11, 2), (4, 11, 1), (16, 36, 1)])
+@pytest.mark.parametrize("case", [0, 1])
+def test_longest_punctured_code_words_in_the_stream(gpu, case, F, nf, shape):
+    """EEP 1-A at 384 kbit/s (36 864 soft bits per CIF) / at 344 kbit/s (33 024: the first rate whose punctured code word outgrows a
+    signed 16-bit index) beside two small classes, through the stream's own readers of the depuncturing map: the state-parallel kernel's
+    gather, and the step tables of the fused kernel's 324-row (4 frames per call) and 96-row (16) builds"""
+    f = factory_lane_per_codeword if shape == 1 else factory_state_parallel
+    P.check_mixed_ensemble(f, F=F, nf=nf, expect_fused=True, subchs=P.big_rate_subchannels(case))
+
+
 @pytest.mark.parametrize("shape", [1, 2])
 def test_stream_with_either_decoder(gpu, shape):
     """the canonical ensemble through both Viterbi kernels explicitly (soft bits, FIBs, MSC bytes of all 18 sub-channels vs the oracle)"""

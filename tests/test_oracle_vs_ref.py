@@ -55,6 +55,16 @@ def test_protection_profiles():
         p = R.orc_prot_uep(br, lv)
         s = rng.randint(-128, 128, p.n_in).astype(np.int8)
         assert np.array_equal(R.ref_uep(br, lv, s), R.orc_msc_deconvolve(p, s)), (br, lv)
+    # ... and the whole space, 304 profiles (tests/test_protection_profiles.py): the device sweeps compare with the oracle on every one of
+    # them, EEP 1-A beyond 32 767 punctured soft bits included
+    profiles = P.all_protection_profiles()
+    assert len(set(profiles)) == 304
+    rng = np.random.RandomState(304)
+    for prof in profiles:
+        p = P.orc_profile(prof)
+        s = rng.randint(-128, 128, p.n_in).astype(np.int8)
+        want = R.ref_uep(prof[1], prof[2], s) if prof[0] == "uep" else R.ref_eep(prof[1], prof[2], prof[3], s)
+        assert np.array_equal(want, R.orc_msc_deconvolve(p, s)), prof
 
 
 def test_fic_random():

@@ -60,6 +60,15 @@ def load_library(path=None):
     return lib
 
 
+def fused_windows(lib, p):
+    """dabphy_test_fused_windows on a loaded library: needs no handle and no device"""
+    n = (C.c_int32 * 3)()
+    r = lib.dabphy_test_fused_windows(C.byref(p), n)
+    if r != 0:
+        raise DabPhyError("dabphy_test_fused_windows: status %d" % r)
+    return tuple(n)
+
+
 class DabPhy:
     def __init__(self, n_ensembles=1, max_frames=1, device=0, lib_path=None, fft_placement=2, disable_coarse=False,
                  want_constellation=True, want_impulse_response=True, demod_chunk=0, pipeline_sync=False, freqsync_method=2, serial_sync=False, exact_batch=True, decode_shape=0, sync_early=0):
@@ -105,6 +114,10 @@ class DabPhy:
 
     def protection_input_bits(self, p):
         return self.lib.dabphy_protection_input_bits(C.byref(p))
+
+    def fused_windows(self, p):
+        """windows of the fused decode's schedule for its three row counts, 0 = no schedule (dabphy_test_fused_windows: host only)"""
+        return fused_windows(self.lib, p)
 
     # ---- unit-level seams
     def demod_frames(self, frames, want_con=True):

@@ -257,7 +257,7 @@ int dabphy_demod_frames(dabphy_handle* h, const float* frames, uint32_t n_frames
     return sync(h);
 }
 
-static int run_lin_decode(dabphy_handle* h, const int8_t* in, size_t in_stride, const int16_t* d_map, int nbits, uint32_t n_cw,
+static int run_lin_decode(dabphy_handle* h, const int8_t* in, size_t in_stride, const map_t* d_map, int nbits, uint32_t n_cw,
                           int dedisperse, uint8_t* out)
 {
     int r;
@@ -293,12 +293,12 @@ int dabphy_msc_deconvolve(dabphy_handle* h, const dabphy_protection* prot, const
 {
     DeviceBind dev_(h);
     if (!h || !prot || !in || !out || n_codewords == 0 || !protection_valid(prot) || prot->nbits > PRBS_MAX_BITS) return DABPHY_ERR_INVALID;
-    const std::vector<int16_t> m = depuncture_map(prot);
+    const std::vector<map_t> m = depuncture_map(prot);
     int r;
-    if ((r = ensure(h, h->map, m.size() * sizeof(int16_t)))) return r;
-    HIPCHK(h, hipMemcpyAsync(h->map.p, m.data(), m.size() * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
+    if ((r = ensure(h, h->map, m.size() * sizeof(map_t)))) return r;
+    HIPCHK(h, hipMemcpyAsync(h->map.p, m.data(), m.size() * sizeof(map_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));     // m goes out of scope on return paths below only after the copy
-    return run_lin_decode(h, in, (size_t)protection_input_bits(prot), h->map.as<int16_t>(), prot->nbits, n_codewords, 1, out);
+    return run_lin_decode(h, in, (size_t)protection_input_bits(prot), h->map.as<map_t>(), prot->nbits, n_codewords, 1, out);
 }
 
 int dabphy_fic_decode(dabphy_handle* h, const int8_t* soft, uint32_t n_frames, uint8_t* fib, uint8_t* crc_ok, int32_t* ratio_percent)
@@ -467,16 +467,16 @@ int apply_subchannels(dabphy_handle* h)
             std::swap(c.map, prev->map); std::swap(c.tiles, prev->tiles);
             for (int v = 0; v < FUSED_VARIANTS; v++) { std::swap(c.steps[v], prev->steps[v]); c.n_windows[v] = prev->n_windows[v]; }
         } else {
-            const std::vector<int16_t> m = depuncture_map(&c.prot);
-            if ((r = ensure(h, c.map, m.size() * sizeof(int16_t)))) return fail(r);
-            if (hipMemcpy(c.map.p, m.data(), m.size() * sizeof(int16_t), hipMemcpyHostToDevice) != hipSuccess) { h->err = "hipMemcpy(depuncturing map) failed"; return fail(DABPHY_ERR_HIP); }
+            const std::vector<map_t> m = depuncture_map(&c.prot);
+            if ((r = ensure(h, c.map, m.size() * sizeof(map_t)))) return fail(r);
+            if (hipMemcpy(c.map.p, m.data(), m.size() * sizeof(map_t), hipMemcpyHostToDevice) != hipSuccess) { h->err = "hipMemcpy(depuncturing map) failed"; return fail(DABPHY_ERR_HIP); }
             // step tiles of the MSC gather kernel (56 trellis steps each): source byte range of every tile
             std::vector<int32_t> tl;
             const int nsteps = c.prot.nbits + 6;
             for (int s0 = 0; s0 < nsteps; s0 += 56) {
                 const int s1 = std::min(nsteps, s0 + 56);
                 int lo = -1, hi = -1;
-                for (int v = 4 * s0; v < 4 * s1; v++) if (m[v] >= 0) { if (lo < 0) lo = m[v]; hi = m[v]; }
+                for (int v = 4 * s0; v < 4 * s1; v++) if (m[v] != MAP_ERASED) { if (lo < 0) lo = m[v]; hi = m[v]; }
                 if (lo < 0) { tl.push_back(0); tl.push_back(0); continue; }
                 const int lo_al = lo & ~3;
                 tl.push_back(lo_al); tl.push_back((hi - lo_al) / 4 + 1);

@@ -37,6 +37,13 @@ constexpr int TII_CARRIER_ROWS = 1537;             // TII: carriers k = -768 .. 
 
 struct cf32 { float re, im; };
 
+// One entry of a depuncturing map (depuncture_map, dabphy_host.cpp): where a bit of the mother code lies in the punctured stream, or
+// MAP_ERASED for a punctured one.  Two bytes, UNSIGNED: EEP 1-A at 384 kbit/s consumes 36 876 soft bits per code word, past int16
+// (docs/history.md: the int16 map wrapped from 344 kbit/s 1-A on and the kernels took the wrapped entries for erasures).
+using map_t = uint16_t;
+constexpr map_t MAP_ERASED = 0xffff;
+__host__ __device__ __forceinline__ int map_index(uint32_t m) { return m == MAP_ERASED ? -1 : (int)m; }   // -1 = erasure
+
 // std::complex<float> operator* as the reference's compiler emits it (libgcc __mulsc3 fast path):
 // (a+bi)(c+di) = (ac - bd) + (ad + bc)i, four multiplies, one subtract, one add, no FMA.
 __host__ __device__ __forceinline__ cf32 cmul(cf32 x, cf32 y)

@@ -8,7 +8,7 @@ namespace {
 // What every trellis step reads, in terms of a wave's window ring of `rows` rows.  Source byte u of the punctured stream sits in window
 // u >> 4 (slot (u >> 4) & 1), column u & 15 -- and, for an MSC class, map16[u & 15] rows below the lane's row base (the time
 // de-interleaver, dab-audio.cpp:138-143; the FIC has none).  Returns false when the kernel's window schedule cannot follow the map.
-bool step_table(const std::vector<int16_t>& m, int nsteps, int n_in, int rows, bool skew, std::vector<MscStep>& st, int& n_windows, int& why)
+bool step_table(const std::vector<map_t>& m, int nsteps, int n_in, int rows, bool skew, std::vector<MscStep>& st, int& n_windows, int& why)
 {
     static const int map16[16] = {0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15};
     const int PITCH = MSC_ROW_PITCH, SLOT = rows * MSC_ROW_PITCH, ZERO = 2 * SLOT;
@@ -18,7 +18,7 @@ bool step_table(const std::vector<int16_t>& m, int nsteps, int n_in, int rows, b
     for (int q = 0; q < nsteps; q++) {
         uint32_t off[4];
         for (int j = 0; j < 4; j++) {
-            const int u = m[4 * q + j];
+            const int u = map_index(m[4 * q + j]);
             if (u < 0) { off[j] = (uint32_t)ZERO; continue; }
             const int w = u >> 4, col = u & 15;
             off[j] = (uint32_t)((w & 1) * SLOT + (skew ? map16[col] : 0) * PITCH + col);
@@ -64,16 +64,30 @@ size_t soft_ens_stride(const dabphy_handle* h)
 
 int fused_class_tables(dabphy_handle* h, const dabphy_protection& prot, bool fic, DevBuf (&steps)[FUSED_VARIANTS], int (&n_windows)[FUSED_VARIANTS])
 {
-    const std::vector<int16_t> m = depuncture_map(&prot);
+    const std::vector<map_t> m = depuncture_map(&prot);
     const int nsteps = prot.nbits + 6, n_in = protection_input_bits(&prot);
     for (int v = 0; v < FUSED_VARIANTS; v++) {
         std::vector<MscStep> st; int nw = 0, why = 0;
         const bool ok = step_table(m, nsteps, n_in, FUSED_ROWS[v], !fic, st, nw, why);
         if (!ok && debug_env("DABPHY_DEBUG")) fprintf(stderr, "dabphy: class nbits %d: no fused decode (window schedule, reason %d)\n", prot.nbits, why);
-        n_windows[v] = ok ? nw : 0;                   // (never 0 for the profiles of EN 300 401; the two-kernel path decodes such a class)
+        n_windows[v] = ok ? nw : 0;                   // (never 0 for the 304 profiles of EN 300 401 and the FIC: tests/test_protection_profiles.py asks dabphy_test_fused_windows; the two-kernel path decodes a class without a schedule)
         int r;
         if ((r = ensure(h, steps[v], st.size() * sizeof(MscStep)))) return r;
         HIPCHK(h, hipMemcpy(steps[v].p, st.data(), st.size() * sizeof(MscStep), hipMemcpyHostToDevice));
+    }
+    return DABPHY_OK;
+}
+
+// The window schedules alone, on the host: what fused_class_tables would record for the class (0 = none for that row count)
+int dabphy_test_fused_windows(const dabphy_protection* prot, int32_t n_windows[FUSED_VARIANTS])
+{
+    if (!prot || !n_windows || !protection_valid(prot) || prot->nbits > PRBS_MAX_BITS) return DABPHY_ERR_INVALID;
+    dabphy_protection pf; protection_fic(&pf);
+    const bool fic = !memcmp(prot, &pf, sizeof pf);           // (the FIC's rows are not skewed by a time de-interleaver)
+    const std::vector<map_t> m = depuncture_map(prot);
+    for (int v = 0; v < FUSED_VARIANTS; v++) {
+        std::vector<MscStep> st; int nw = 0, why = 0;
+        n_windows[v] = step_table(m, prot->nbits + 6, protection_input_bits(prot), FUSED_ROWS[v], !fic, st, nw, why) ? nw : 0;
     }
     return DABPHY_OK;
 }
@@ -123,7 +137,7 @@ int fused_plan(dabphy_handle* h, uint32_t F, bool want_fic)
         const int P = (int)c.pairs.size();
         if (!h->fused_msc || (!use_sp && (c.n_windows[v] <= 0 || !reach_ok(ens_span(c.pairs))))) continue;
         FusedClass fc{};
-        fc.steps = c.steps[v].as<MscStep>(); fc.pairs = c.pair_tab.as<MscPair>(); fc.map = c.map.as<int16_t>(); fc.out = c.out.as<uint8_t>();
+        fc.steps = c.steps[v].as<MscStep>(); fc.pairs = c.pair_tab.as<MscPair>(); fc.map = c.map.as<map_t>(); fc.out = c.out.as<uint8_t>();
         fc.nbits = c.prot.nbits; fc.nsteps = fc.nbits + 6; fc.n_windows = c.n_windows[v]; fc.n_cw = (int32_t)(4 * F * (uint32_t)P);
         fc.n_pairs = P; fc.kind = 0; fc.dedisperse = 1;
         items.push_back({fc.nsteps, (int)cls.size(), (fc.n_cw + 63) / 64});

@@ -232,15 +232,19 @@ bool protection_valid(const dabphy_protection* p)
     return blocks * 128 == 4 * p->nbits;
 }
 
-std::vector<int16_t> depuncture_map(const dabphy_protection* p)
+// Every caller refuses code words of more than PRBS_MAX_BITS bits first (dabphy_msc_deconvolve, dabphy_set_subchannels): 288 blocks of
+// at most 4 * (8 + 24) soft bits and the 12 of the tail -- every index a profile that protection_valid accepts can produce is below MAP_ERASED
+static_assert((PRBS_MAX_BITS / 32) * 4 * (8 + 24) + 12 < MAP_ERASED, "a depuncturing map entry must hold every punctured index");
+
+std::vector<map_t> depuncture_map(const dabphy_protection* p)
 {
     const HostTables& T = host_tables();
-    std::vector<int16_t> m((size_t)4 * p->nbits + 24, -1);
+    std::vector<map_t> m((size_t)4 * p->nbits + 24, MAP_ERASED);
     int in = 0, v = 0;
     for (int s = 0; s < 4; s++)
         for (int i = 0; i < p->L[s]; i++)
-            for (int j = 0; j < 128; j++) { if (T.pcodes[p->PI[s] - 1][j % 32]) m[v] = (int16_t)in++; v++; }
-    for (int i = 0; i < 24; i++) { if ((i & 3) < 2) m[v] = (int16_t)in++; v++; }     // PI_X = 1100 x 6 (fic-handler.cpp:39-42)
+            for (int j = 0; j < 128; j++) { if (T.pcodes[p->PI[s] - 1][j % 32]) m[v] = (map_t)in++; v++; }
+    for (int i = 0; i < 24; i++) { if ((i & 3) < 2) m[v] = (map_t)in++; v++; }     // PI_X = 1100 x 6 (fic-handler.cpp:39-42)
     return m;
 }
 

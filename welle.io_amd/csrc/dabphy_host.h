@@ -32,6 +32,6 @@ int protection_uep(dabphy_protection* p, int bitrate, int level);
 int uep_table_entry(int table_index, int* size_cu, int* level, int* bitrate);
 int protection_input_bits(const dabphy_protection* p);
 bool protection_valid(const dabphy_protection* p);
-std::vector<int16_t> depuncture_map(const dabphy_protection* p);   // mother-code index -> punctured index, -1 = erasure
+std::vector<map_t> depuncture_map(const dabphy_protection* p);     // mother-code index -> punctured index, MAP_ERASED = erasure (dabphy_common.h)
 
 } // namespace dabphy

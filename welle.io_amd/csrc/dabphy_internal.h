@@ -70,7 +70,7 @@ struct dabphy_handle {
     char devname[256] = {0};
     // constant tables in HBM
     cf32 *d_tw = nullptr, *d_ref = nullptr, *d_nco = nullptr;
-    int16_t* d_bin2soft = nullptr; uint32_t* d_prbs_words = nullptr; int16_t* d_fic_map = nullptr;
+    int16_t* d_bin2soft = nullptr; uint32_t* d_prbs_words = nullptr; map_t* d_fic_map = nullptr;
     int32_t* d_osc_unsafe = nullptr; unsigned long long* d_osc_stats = nullptr;   // osc_exact.h: unsafe table entries; symbols mixed unchecked / checked
     Tables tab{};
     // grow-only scratch

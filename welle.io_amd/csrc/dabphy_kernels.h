@@ -132,7 +132,7 @@ struct FicGatherArgs {
     const int8_t* soft; int soft_ring; size_t frame_stride;   // bytes between frame slots (SOFT_PER_FRAME in the ring)
     size_t soft_ens_stride;                                   // bytes between ensembles (0: soft_ring * frame_stride)
     const FrameDesc* desc; int n_ens, n_frames;
-    const int16_t* map;     // [3096] mother-code index -> index into the 2304 punctured bits, -1 = erasure
+    const map_t* map;       // [3096] mother-code index -> index into the 2304 punctured bits, MAP_ERASED = erasure
     VitClass c;
     int frame_sel;          // 0: every frame of the batch, codeword (b F + f) 4 + q; f + 1: frame f only, codeword 4 b + q (c.n_cw = 4 B)
 };
@@ -158,7 +158,7 @@ void launch_pair_cif0(MscPair* pairs, int n_pairs, const FrameDesc* desc, int n_
 struct MscGatherArgs {
     const int8_t* soft; int soft_ring; const RxState* state; int n_ens, n_frames;
     size_t soft_ens_stride;   // bytes between ensembles (0: soft_ring * SOFT_PER_FRAME)
-    const int16_t* map;     // [4*nbits+24] -> index into the sub-channel's length*64 soft bits, -1 = erasure
+    const map_t* map;       // [4*nbits+24] -> index into the sub-channel's length*64 soft bits, MAP_ERASED = erasure
     const MscPair* pairs;     // [n_pairs] the (ensemble, sub-channel) pairs of the class
     const int32_t* tiles;     // [ceil(nsteps/56)][2]: first source byte (4-aligned) and dwords per row of each step tile
     int n_pairs;
@@ -190,7 +190,7 @@ constexpr uint32_t MSC_FIRST_USE = 1u << 15, MSC_LOAD_NEXT = 1u << 31, MSC_OFF_M
 struct FusedClass {
     const MscStep* steps;     // [nsteps + 6] for the launch's row-count variant
     const MscPair* pairs;     // MSC: [n_pairs] (ensemble, start bit) of every pair, ensembles ascending
-    const int16_t* map;       // [4 * nsteps] mother-code index -> index into the class's punctured bit stream, -1 = erasure (k_viterbi_sp gathers by it)
+    const map_t* map;         // [4 * nsteps] mother-code index -> index into the class's punctured bit stream, MAP_ERASED = erasure (k_viterbi_sp gathers by it)
     uint8_t* out;             // [n_cw][nbits / 8]
     int32_t nsteps, nbits, n_windows, n_cw, n_pairs, kind, dedisperse, reserved_;
 };
@@ -246,7 +246,7 @@ struct CrcArgs {
 // Gather from a plain [n_cw][in_stride] array of soft bits (the Viterbi::deconvolve / Protection::deconvolve seams)
 struct LinGatherArgs {
     const int8_t* in; size_t in_stride;
-    const int16_t* map;     // nullptr: input is already depunctured (index = 4*step + j)
+    const map_t* map;       // nullptr: input is already depunctured (index = 4*step + j)
     VitClass c;
 };
 

@@ -309,7 +309,7 @@ static int decode_unfused_classes(dabphy_handle* h, const Batch& b)
         if ((r = prepare_class(h, c, cls.prot.nbits, (int)(4 * b.F * (uint32_t)P), 1))) return r;
         c.out = cls.out.as<uint8_t>();
         MscGatherArgs g{}; g.soft = b.da.soft; g.soft_ring = b.ring_frames; g.soft_ens_stride = b.ens_stride; g.state = h->d_state; g.n_ens = (int)b.B; g.n_frames = (int)b.F;
-        g.map = cls.map.as<int16_t>(); g.pairs = cls.pair_tab.as<MscPair>(); g.tiles = cls.tiles.as<int32_t>(); g.n_pairs = P; g.desc = b.d_desc; g.c = c;
+        g.map = cls.map.as<map_t>(); g.pairs = cls.pair_tab.as<MscPair>(); g.tiles = cls.tiles.as<int32_t>(); g.n_pairs = P; g.desc = b.d_desc; g.c = c;
         if (first_two) mark(h, dabphy_handle::ST_MSC_GATHER, false);
         launch_msc_gather(g, h->stream);
         VitArgs v{}; v.c = c; v.prbs_words = h->d_prbs_words;

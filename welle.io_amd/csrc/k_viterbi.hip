@@ -151,7 +151,7 @@ __global__ void __launch_bounds__(256) k_fic_gather(FicGatherArgs A)
         uint32_t word = 0;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            const int u = A.map[4 * s + j];
+            const int u = map_index(A.map[4 * s + j]);
             int v = (u >= 0 && live && d.valid == 1) ? (int)src[u] : 0;
             v += 127; v = v < 0 ? 0 : v; v = v > 255 ? 255 : v;
             word |= (uint32_t)v << (8 * j);
@@ -234,7 +234,7 @@ __global__ void __launch_bounds__(256) k_msc_gather(MscGatherArgs A)
             uint32_t word = 0;
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                const int u = A.map[4 * s + j];
+                const int u = map_index(A.map[4 * s + j]);
                 int v = 0;
                 if (u >= 0 && live) {
                     const long long c_src = c_glob - 16 + map16[u & 15];
@@ -255,7 +255,7 @@ __global__ void __launch_bounds__(256) k_msc_gather(MscGatherArgs A)
         const int s1 = (s0 + GT_STEPS < nsteps) ? s0 + GT_STEPS : nsteps;
         // map entry -> byte offset inside a tile row plus the row shift of the time de-interleaver; -1 = erasure
         if (t < 4 * (s1 - s0)) {
-            const int u = A.map[4 * s0 + t];
+            const int u = map_index(A.map[4 * s0 + t]);
             s_map[t] = (u >= 0) ? (map16[u & 15] * (GT_PITCHW * 4) + (u - u_lo)) : -1;
         }
         // rows travel HBM -> LDS by LDS-DMA: nothing waits between the (up to 28) row requests of a wave
@@ -687,7 +687,7 @@ __global__ void __launch_bounds__(256) k_lin_gather(LinGatherArgs A)
         uint32_t word = 0;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            const int u = A.map ? (int)A.map[4 * s + j] : 4 * s + j;
+            const int u = A.map ? map_index(A.map[4 * s + j]) : 4 * s + j;
             int v = (live && u >= 0) ? (int)src[u] : 0;
             v += 127; v = v < 0 ? 0 : v; v = v > 255 ? 255 : v;
             word |= (uint32_t)v << (8 * j);

@@ -87,14 +87,14 @@ __global__ void __launch_bounds__(64, OCC) k_viterbi_sp(FusedArgs A)
     }
     __syncthreads();
     {
-        const int16_t* __restrict__ map = C.map;
+        const map_t* __restrict__ map = C.map;
         for (int s = lane; s < nsteps; s += 64) {
             uint2 mm = make_uint2(0, 0);
             if (map) mm = *reinterpret_cast<const uint2*>(map + 4 * s);                    // four map entries
             int v[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                const int u = map ? (int)(int16_t)(((j < 2 ? mm.x : mm.y) >> (16 * (j & 1))) & 0xffffu) : 4 * s + j;
+                const int u = map ? map_index(((j < 2 ? mm.x : mm.y) >> (16 * (j & 1))) & 0xffffu) : 4 * s + j;
                 long long off = -1;
                 if (u >= 0) off = s_rowoff[u & 15];
                 v[j] = off >= 0 ? (int)base[off + u] : 0;

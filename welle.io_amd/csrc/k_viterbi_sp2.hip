@@ -96,14 +96,14 @@ __global__ void __launch_bounds__(64, OCC) k_viterbi_sp2(FusedArgs A)
     __syncthreads();
     // the table of steps [c0, c0 + n): entry (s - c0)
     auto fill = [&](int c0, int n) {
-        const int16_t* __restrict__ map = C.map;
+        const map_t* __restrict__ map = C.map;
         for (int s = c0 + j; s < c0 + n; s += 32) {
             uint2 mm = make_uint2(0, 0);
             if (map) mm = *reinterpret_cast<const uint2*>(map + 4 * s);                    // four map entries
             int v[4];
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-                const int u = map ? (int)(int16_t)(((q < 2 ? mm.x : mm.y) >> (16 * (q & 1))) & 0xffffu) : 4 * s + q;
+                const int u = map ? map_index(((q < 2 ? mm.x : mm.y) >> (16 * (q & 1))) & 0xffffu) : 4 * s + q;
                 long long off = -1;
                 if (u >= 0) off = s_rowoff[half][u & 15];
                 v[q] = off >= 0 ? (int)base[off + u] : 0;
