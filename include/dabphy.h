@@ -504,7 +504,10 @@ int dabphy_mp2_check(dabphy_handle* h, const uint8_t* frames, uint32_t n_streams
  * dabphy_get_tii returns what onTIIMeasurement (radio-controller.h:128) would have been called with during the last batch:
  * out [n_ensembles][max_per_ensemble], n[b] = measurements of ensemble b (may exceed what was stored), ordered by frame, then by
  * (comb, pattern) -- the reference's order inside one frame is unspecified.  Up to 32 comb/pattern pairs are tracked per
- * ensemble (the reference's map is unbounded). */
+ * ensemble (the reference's map is unbounded): the first 32 an ensemble meets since dabphy_set_tii first switched the side path on
+ * or the last dabphy_reset, ghost pairs of a noisy frame included, keep their slots for good; measurements of any further pair are
+ * not summed and never reported, only counted (dabphy_test_tii_dropped, include/dabphy_test.h).  A network of more than 32 pairs,
+ * which the reference follows, is therefore reported in part; dabphy_reset frees the slots. */
 typedef struct {
     int32_t frame;                       /* frame of the batch whose NULL symbol completed the 5th measurement */
     int32_t comb, pattern;               /* tii_measurement_t (radio-controller.h:56-63) */

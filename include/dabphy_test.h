@@ -61,6 +61,18 @@ int dabphy_last_decode_plan(dabphy_handle* h, int32_t* shape, int32_t* fused_cla
  * two-kernel path: same bytes, one more pass through HBM). */
 int dabphy_test_fused_windows(const dabphy_protection* prot, int32_t n_windows[3]);
 
+/* The TII side path (k_tii_measure + k_tii_accumulate, the launch dabphy_process makes) on host-supplied (NULL symbol, PRS) pairs as
+ * OFDMProcessor hands them to TIIDecoder::pushSymbols: null [n_ens][n_frames][2656] and prs [n_ens][n_frames][2048] cf32,
+ * valid [n_ens][n_frames] = FrameDesc::valid of each frame (only 1 = demodulated is analysed).  The pairs are laid out as frames in a
+ * device buffer (PRS at the frame start, NULL symbol 2048 + 75 * 2552 samples behind it) with the oscillator at rest, so the kernels see
+ * the samples unchanged.  The handle's own sums, tables and event buffers are used: the 5-frame sums carry from call to call and into
+ * dabphy_process, dabphy_get_tii returns this call's measurements, dabphy_reset starts over.  n_ens = the handle's n_ensembles,
+ * 1 <= n_frames <= max_frames; DABPHY_ERR_INVALID otherwise, and unless dabphy_set_tii(h, 1) has been called. */
+int dabphy_test_tii_pairs(dabphy_handle* h, const float* null, const float* prs, const int32_t* valid, uint32_t n_ens, uint32_t n_frames);
+/* Measurements per ensemble that were analysed but not added to any sum because all 32 slots of the ensemble were taken by other
+ * comb/pattern pairs, since dabphy_set_tii switched the side path on for the first time or the last dabphy_reset. */
+int dabphy_test_tii_dropped(dabphy_handle* h, int32_t* per_ensemble);
+
 #ifdef __cplusplus
 }
 #endif

@@ -888,8 +888,8 @@ static void tii_carriers(int comb, int pattern, int* carriers /* 32 */)
             if (tii_pat(pattern, b)) { const int k = 1 + 2 * comb + 48 * b; carriers[n++] = k + off[g]; carriers[n++] = k + off[g] + 1; }
 }
 
-int orc_tii_frame(orc_tii_state* st, const orc_cf32* null2656, const orc_cf32* prs2048, const int32_t* rank,
-                  orc_tii_event* ev, int max_ev, uint8_t* detect192)
+int orc_tii_frame_ties(orc_tii_state* st, const orc_cf32* null2656, const orc_cf32* prs2048, const int32_t* rank,
+                       orc_tii_event* ev, int max_ev, uint8_t* detect192, int32_t* ties)
 {
     tii_init();
     static _Thread_local orc_cf32 n[ORC_TU], p[ORC_TU];
@@ -945,6 +945,11 @@ int orc_tii_frame(orc_tii_state* st, const orc_cf32* null2656, const orc_cf32* p
             int best = 0;
             for (int e = 1; e < ORC_TII_NERR; e++)
                 if (meas->acc[e] < meas->acc[best] || (meas->acc[e] == meas->acc[best] && rk[e] < rk[best])) best = e;
+            if (ties && n_ev < max_ev) {                                          /* how the winner was decided: candidates at the minimum, the map's generation */
+                int at_min = 0;
+                for (int e = 0; e < ORC_TII_NERR; e++) at_min += meas->acc[e] == meas->acc[best];
+                ties[2 * n_ev] = at_min; ties[2 * n_ev + 1] = meas->cycle;
+            }
             if (n_ev < max_ev) {
                 ev[n_ev].comb = comb; ev[n_ev].pattern = pattern;
                 ev[n_ev].error = (float)meas->acc[best];                          /* m.error = best->second */
@@ -956,6 +961,12 @@ int orc_tii_frame(orc_tii_state* st, const orc_cf32* null2656, const orc_cf32* p
         }
     }
     return n_ev;
+}
+
+int orc_tii_frame(orc_tii_state* st, const orc_cf32* null2656, const orc_cf32* prs2048, const int32_t* rank,
+                  orc_tii_event* ev, int max_ev, uint8_t* detect192)
+{
+    return orc_tii_frame_ties(st, null2656, prs2048, rank, ev, max_ev, detect192, NULL);
 }
 
 /* ------------------------------------------------------------------------------------------ receiver */

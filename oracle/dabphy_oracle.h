@@ -115,7 +115,9 @@ void orc_rs_encode120(const uint8_t* data110, uint8_t* parity10);          /* en
 /* TII (tii-decoder.cpp:189-383): one (NULL symbol, PRS) pair per call, every frame looked at.  rank[2][504] = position of
  * key float(err), err = -4..499, in the iteration order of the reference's unordered_map<float, uint64_t> when it is
  * filled for the first time ([0]) and refilled after clear() ([1]) -- see oracle/tii_order.cpp.  Returns the number of
- * onTIIMeasurement calls, in ascending (comb, pattern) order (the reference's order within a frame is unspecified). */
+ * onTIIMeasurement calls, in ascending (comb, pattern) order (the reference's order within a frame is unspecified).
+ * orc_tii_frame_ties is the same pass with one more output, ties (optional, [max_ev][2]): for each report, how many of the 504
+ * candidates held the minimum sum (2 or more: the iteration order decided) and the cycle whose rank row was consulted. */
 #define ORC_TII_NERR 504
 typedef struct { int32_t frame, comb, pattern, delay_samples; float error; } orc_tii_event;
 typedef struct orc_tii_state orc_tii_state;
@@ -123,6 +125,8 @@ size_t orc_tii_state_bytes(void);
 void orc_tii_reset(orc_tii_state* st);
 int orc_tii_frame(orc_tii_state* st, const orc_cf32* null2656, const orc_cf32* prs2048, const int32_t* rank,
                   orc_tii_event* ev, int max_ev, uint8_t* detect192);
+int orc_tii_frame_ties(orc_tii_state* st, const orc_cf32* null2656, const orc_cf32* prs2048, const int32_t* rank,
+                       orc_tii_event* ev, int max_ev, uint8_t* detect192, int32_t* ties);
 void orc_tii_iteration_rank(int32_t* rank2x504);                            /* oracle/tii_order.cpp */
 
 /* Full receiver: ofdm-processor.cpp:235-501 driving all of the above in lock step. */

@@ -653,7 +653,7 @@ def check_tii_vs_oracle(d_factory, F=4, nf=17, snr_db=20, cfo=70, pipeline_sync=
         for b in range(B):
             nfr = nvalid[b]
             w = [e for e in want[b]["tii"] if e[0] < nfr]
-            assert sorted(got[b]) == w, "TII measurements of ensemble %d differ:\n got  %s\n want %s" % (b, sorted(got[b]), w)
+            assert got[b] == w, "TII measurements of ensemble %d differ (in the order returned):\n got  %s\n want %s" % (b, got[b], w)
             assert nfr >= want[b]["n_frames"] - F * (2 if pipeline_sync else 1)
         if stats is not None:
             stats["replayed"] = d.replayed_batches()
@@ -1973,3 +1973,331 @@ DEFERRED_SIDE_DOORS = {
 
 def check_deferred_side_door(d_factory, name):
     DEFERRED_SIDE_DOORS[name](d_factory)
+
+
+# ------------------------------------------------------------------------------------------ TII on (NULL, PRS) pairs
+# The TII kernels driven pair by pair (dabphy_test_tii_pairs: the launch dabphy_process makes, on frames built from the pairs) against
+# the TIIDecoder restatement fed the same pairs, which tests/test_oracle_vs_ref.py pins to the real class on the same sets.  Pairs are
+# synthesised here: no streams, a few hundred kilobytes per ensemble.
+
+def tii_synth_pairs(frames, snr_db, seed, early=100):
+    """(NULL [F][2656], PRS [F][2048]) as OFDMProcessor cuts them with the FFT window `early` samples inside the prefix.  frames: per
+    frame, the transmitters (comb, pattern, delay_samples, gain) whose TII fills the NULL symbol, each delayed by its own delay against
+    the PRS; complex white noise at snr_db under a unit-gain carrier (None: no noise).  The spectrum has unit carriers."""
+    rng = np.random.RandomState(seed)
+    pf = synth.prs_freq()
+    m = np.arange(2048)
+    F = len(frames)
+    nul = np.zeros((F, 2656), np.complex128); prs = np.zeros((F, 2048), np.complex128)
+    t_prs = np.roll(np.fft.ifft(pf), early)
+    for f, txs in enumerate(frames):
+        zn = np.zeros(2048, np.complex128)
+        for comb, pattern, delay, gain in txs:
+            z = np.zeros(2048, np.complex128)
+            for k in synth.tii_carriers(comb, pattern)[0::2]:          # both carriers of a pair carry the PRS phase of the first
+                z[k % 2048] = z[(k + 1) % 2048] = pf[k % 2048] * gain
+            zn += z * np.exp(-2j * np.pi * m * (early + delay) / 2048)   # = the useful part rolled by early + delay
+        u = np.fft.ifft(zn)
+        nul[f] = np.concatenate([u[-608:], u])
+        prs[f] = t_prs
+    if snr_db is not None:
+        sigma = np.sqrt(0.5 / 2048 / 10 ** (snr_db / 10))
+        prs += sigma * (rng.randn(F, 2048) + 1j * rng.randn(F, 2048))
+        nul += sigma * (rng.randn(F, 2656) + 1j * rng.randn(F, 2656))
+    return nul.astype(np.complex64), prs.astype(np.complex64)
+
+
+def tii_oracle_pairs(nul, prs, valid=None, threads=8):
+    """the restatement over [B][F] pairs, ensemble by ensemble, fed the frames with valid == 1 only -> (events [B] in the order made:
+    (frame of the batch, comb, pattern, delay_samples, error), ties [B])"""
+    from concurrent.futures import ThreadPoolExecutor
+    B, F = nul.shape[:2]
+    valid = np.ones((B, F), np.int32) if valid is None else np.asarray(valid)
+
+    def one(b):
+        idx = np.flatnonzero(valid[b] == 1)
+        ev, ties = R.orc_tii_events(nul[b][idx], prs[b][idx]) if len(idx) else ([], [])
+        return [(int(idx[e[0]]),) + e[1:] for e in ev], ties
+    with ThreadPoolExecutor(threads) as ex:                            # (the library call releases the interpreter lock)
+        res = list(ex.map(one, range(B)))
+    return [r[0] for r in res], [r[1] for r in res]
+
+
+def tii_device_pairs(d, nul, prs, valid=None, calls=None, max_per_ensemble=None):
+    """dabphy_test_tii_pairs over [B][F] pairs in calls of calls[i] frames (default: one call) -> (events [B] in the order dabphy_get_tii
+    returns them, frames numbered over all calls, n [B] summed over the calls)"""
+    B, F = nul.shape[:2]
+    calls = [F] if calls is None else list(calls)
+    assert sum(calls) == F
+    got = [[] for _ in range(B)]; total = np.zeros(B, np.int64); f0 = 0
+    for nf in calls:
+        d.test_tii_pairs(nul[:, f0:f0 + nf], prs[:, f0:f0 + nf], None if valid is None else np.asarray(valid)[:, f0:f0 + nf])
+        ev, n = d.tii(max_per_ensemble)
+        for b in range(B):
+            assert max_per_ensemble is not None or n[b] == len(ev[b])
+            got[b] += [(f0 + int(e["frame"]), int(e["comb"]), int(e["pattern"]), int(e["delay_samples"]), float(e["error"])) for e in ev[b]]
+        total += n; f0 += nf
+    return got, total
+
+
+def tii_pairs_handle(d_factory, B, max_frames):
+    d = d_factory(n_ensembles=B, max_frames=max_frames, want_constellation=False, want_impulse_response=False)
+    d.set_tii(True)
+    return d
+
+
+def tii_synth_set(ens_frames, snr_db, seed, early=100):
+    """tii_synth_pairs for every ensemble of a batch (snr_db, early: one value, or one per ensemble) -> NULL [B][F][2656], PRS [B][F][2048]"""
+    B = len(ens_frames)
+    snr = snr_db if isinstance(snr_db, (list, tuple)) else [snr_db] * B
+    seeds = seed if isinstance(seed, (list, tuple)) else [seed + b for b in range(B)]
+    pairs = [tii_synth_pairs(ens_frames[b], snr[b], seeds[b], early if isinstance(early, int) else early[b]) for b in range(B)]
+    return np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
+
+
+def tii_likely_from_detect(det):
+    """the comb * 70 + pattern values TIIDecoder::run analyses, ascending, from the 192 detection flags of one pair (tii-decoder.cpp:308-327):
+    all four carriers of the pattern detected; 10 or more: the frame is skipped"""
+    lk = [c * 70 + p for c in range(24) for p in range(70) if all(det[c + 24 * b] for b in range(8) if (synth.TII_PATTERNS[p] >> (7 - b)) & 1)]
+    return lk if len(lk) < 10 else []
+
+
+_TII_CACHE = {}
+
+
+def _tii_cached(key, make):
+    if key not in _TII_CACHE:
+        _TII_CACHE[key] = make()
+    return _TII_CACHE[key]
+
+
+def _pat(bits):
+    return synth.TII_PATTERNS.index(bits)
+
+
+TII_END_PAIRS = ((0, 69), (23, 0))             # carrier -768 = first row of the rotator table, carrier 768 = its last
+TII_DELAYS = [-4, 499, 0, 1, 7, 13, 25, 37, 50, 64, 81, 100, 128, 150, 177, 211, 256, 300, 333, 380, 401, 450, 477, 490, 498, -3, -1, 2]
+
+
+def tii_set_every_pair(full):
+    """all 24 x 70 comb/pattern pairs, once each: 210 ensembles of 8 transmitters on 8 different combs (no ghosts: pairs on different
+    combs share no carrier), delays from both ends of the candidate range and between, gains 0.5 .. 1, 6 frames at 15 dB.  full = False: the
+    11 of those ensembles that hold every comb, every pattern and the two table-end pairs."""
+    def make():
+        def ens(e):
+            g, q = divmod(e, 70)
+            net = [(8 * g + j, (q + 9 * j) % 70, TII_DELAYS[(5 * e + 3 * j) % len(TII_DELAYS)], 0.5 + 0.1 * ((e + 2 * j) % 6)) for j in range(8)]
+            return [t[:2] + ({TII_END_PAIRS[0]: -4, TII_END_PAIRS[1]: 499}.get(t[:2], t[2]),) + t[3:] for t in net]
+        es = list(range(210)) if full else sorted({70 * (q % 3) + q for q in range(9)} | {69, 147})
+        nets = [ens(e) for e in es]
+        nul, prs = tii_synth_set([[n] * 6 for n in nets], 15, [900 + e for e in es])
+        want, ties = tii_oracle_pairs(nul, prs)
+        return nets, nul, prs, want
+    return _tii_cached(("every", full), make)
+
+
+def check_tii_pairs_every_pair(d_factory, full=True):
+    """every comb/pattern pair through k_tii_measure / k_tii_accumulate: the whole pattern table, every comb's carriers, both ends of the
+    rotator table, both ends of the candidate-delay range; the sums straddle two calls at every split of the 5-frame cycle"""
+    nets, nul, prs, want = tii_set_every_pair(full)
+    B = len(nets)
+    seen = {e[1:3] for w in want for e in w}
+    planned = {t[:2] for n in nets for t in n}
+    assert seen == planned and all(len(w) == 8 for w in want), "the oracle does not report every planned pair: missing %s" % sorted(planned - seen)
+    assert set(TII_END_PAIRS) <= seen
+    if full:
+        assert len(seen) == 24 * 70
+    else:
+        assert {c for c, p in seen} == set(range(24)) and {p for c, p in seen} == set(range(70))
+    delays = {e[3] for w in want for e in w}
+    assert -4 in delays and 499 in delays and len(delays - {-4, 499}) >= 20, sorted(delays)
+    d = tii_pairs_handle(d_factory, B, 5)
+    try:
+        for calls in ([1, 5], [2, 4], [3, 3]):
+            d.reset()
+            got, n = tii_device_pairs(d, nul, prs, calls=calls)
+            for b in range(B):
+                ends = [t[:2] for t in nets[b] if t[:2] in TII_END_PAIRS]
+                assert got[b] == want[b], "calls of %s frames, ensemble %d %s%s:\n got  %s\n want %s" % (
+                    calls, b, [t[:2] for t in nets[b]], " (holds the table-end pair %s)" % ends if ends else "", got[b], want[b])
+            assert (d.test_tii_dropped() == 0).all()
+    finally:
+        d.close()
+
+
+def tii_set_likely_limit():
+    """B = 4, F = 12.  Ensemble 0: nine transmitters on nine combs (A: analysed) and the same plus a tenth (S: 10 likely pairs, skipped).
+    Ensembles 1, 2: A in every frame, some frames not demodulated (valid 0, 2, 3).  Ensemble 3: two patterns on one comb that share three
+    blocks (G: 5 likely pairs, three of them ghosts), that share two (15 likely) and none (70 likely): both skipped."""
+    def make():
+        A = [(c, (7 * c + 3) % 70, 20 * i, 0.6 + 0.05 * (i % 5)) for i, c in enumerate((0, 2, 5, 8, 11, 14, 17, 20, 23))]
+        S = A + [(22, 31, 60, 0.8)]
+        G = [(6, _pat(0b11110000), 10, 0.8), (6, _pat(0b11101000), 70, 0.7)]
+        X2 = [(6, _pat(0b11110000), 10, 0.8), (6, _pat(0b11001100), 70, 0.7)]
+        X0 = [(6, _pat(0b11110000), 10, 0.8), (6, _pat(0b00001111), 70, 0.7)]
+        frames = [[A, A, S, A, A, A, A, A, A, S, A, A],
+                  [A] * 12, [A] * 12,
+                  [G, G, X2, G, G, G, X0, G, G, G, G, G]]
+        valid = np.ones((4, 12), np.int32)
+        valid[1, [1, 8]] = [0, 2]
+        valid[2, [0, 6]] = [3, 0]
+        # the frames that are analysed: every fifth one completes the measurements
+        analysed = [[f for f in range(12) if valid[b, f] == 1 and frames[b][f] not in (S, X2, X0)] for b in range(4)]
+        reports = [a[4::5] for a in analysed]
+        nul, prs = tii_synth_set(frames, 20, 300)
+        want, ties = tii_oracle_pairs(nul, prs, valid)
+        return nul, prs, valid, want, reports
+    return _tii_cached("limit", make)
+
+
+def check_tii_pairs_likely_limit(d_factory):
+    """9 likely pairs are analysed, 10 or more skip the frame (tii-decoder.cpp:327) and leave sums and counts alone, like a frame that was
+    not demodulated; ghost pairs are analysed and reported like real ones"""
+    nul, prs, valid, want, reports = tii_set_likely_limit()
+    assert reports == [[5, 11]] * 4                                     # = frames 4 and 9 + one frame skipped or not demodulated in each cycle
+    for b, per in enumerate((9, 9, 9, 5)):
+        frames = [e[0] for e in want[b]]
+        assert frames == [f for f in reports[b] for _ in range(per)], "ensemble %d: the oracle reports in frames %s, planned %s x %d" % (b, frames, reports[b], per)
+    assert len({e[1:3] for e in want[3]}) == 5 and {e[1] for e in want[3]} == {6}
+    d = tii_pairs_handle(d_factory, 4, 12)
+    try:
+        for calls in ([12], [3, 4, 5]):
+            d.reset()
+            got, n = tii_device_pairs(d, nul, prs, valid, calls=calls)
+            for b in range(4):
+                assert got[b] == want[b], "calls of %s frames, ensemble %d:\n got  %s\n want %s" % (calls, b, got[b], want[b])
+            assert (d.test_tii_dropped() == 0).all()
+    finally:
+        d.close()
+
+
+def tii_set_slot_exhaustion():
+    """Ensemble 0 meets 40 comb/pattern pairs, 9 + 8 + 8 + 8 + 7 in its first five frames, and each group returns every fifth frame: 50
+    frames = two reports per pair.  Ensemble 1: three pairs in every frame."""
+    def make():
+        cps = [(c, (11 * c + 5 * g) % 70) for g in range(5) for c in range(23, -1, -1)][:45]
+        groups = []; at = 0
+        for size in (9, 8, 8, 8, 7):
+            groups.append([(c, p, 15 * i + 3 * len(groups), 0.7) for i, (c, p) in enumerate(sorted(cps[at:at + size], key=lambda t: t[0]))]); at += 9
+        small = [(1, 4, 0, 0.9), (9, 44, 120, 0.7), (19, 67, 333, 0.6)]
+        frames = [[groups[f % 5] for f in range(50)], [small] * 50]
+        nul, prs = tii_synth_set(frames, 20, 500)
+        want = []; likely = []
+        for b in range(2):
+            ev, ties, det = R.orc_tii_events(nul[b], prs[b], want_detect=True)
+            want.append(ev); likely.append([tii_likely_from_detect(x) for x in det])
+        return nul, prs, want, likely
+    return _tii_cached("slots", make)
+
+
+def check_tii_pairs_slot_exhaustion(d_factory):
+    """the device tracks TII_SLOTS = 32 pairs per ensemble: the first 32 it meets (frame by frame, ascending comb * 70 + pattern inside a
+    frame) are measured exactly like the reference measures them, the measurements of the others are dropped and counted"""
+    nul, prs, want, likely = tii_set_slot_exhaustion()
+    order = []
+    for lk in likely[0]:
+        order += [cp for cp in lk if cp not in order]
+    new_per_frame = [len(set(lk) - {cp for prev in likely[0][:f] for cp in prev}) for f, lk in enumerate(likely[0])]
+    assert len(order) == 40 and max(new_per_frame) == 9, (len(order), new_per_frame)
+    kept = set(order[:32])
+    want0 = [e for e in want[0] if e[1] * 70 + e[2] in kept]
+    dropped0 = sum(1 for lk in likely[0] for cp in lk if cp not in kept)
+    assert len(want0) == 64 and len(want[0]) == 80 and dropped0 == 80 and len(want[1]) == 30 and len({cp for lk in likely[1] for cp in lk}) == 3
+    d = tii_pairs_handle(d_factory, 2, 10)
+    try:
+        for again in range(2):
+            got, n = tii_device_pairs(d, nul, prs, calls=[10] * 5)
+            assert got[0] == want0, "%s: the ensemble with 40 pairs:\n got  %s\n want %s" % ("after dabphy_reset" if again else "first run", got[0], want0)
+            assert got[1] == want[1], "the ensemble with 3 pairs beside it:\n got  %s\n want %s" % (got[1], want[1])
+            assert d.test_tii_dropped().tolist() == [dropped0, 0]
+            d.reset()
+            assert d.test_tii_dropped().tolist() == [0, 0]
+    finally:
+        d.close()
+
+
+def tii_set_ties():
+    """four ensembles of nine weak transmitters with five echoes each, at 14 and 17 dB: error sums with several near-equal minima.  The seeds
+    were searched with the oracle for reports whose minimum is shared (R.orc_tii_events: ties), in both generations of the sums' map"""
+    def make():
+        cps = [(0, 3), (2, 69), (5, 17), (8, 40), (11, 22), (14, 55), (17, 9), (20, 33), (23, 61)]
+        net = [(c, p, dl, 0.4) for c, p in cps for dl in (0, 90, 170, 260, 350, 440)]
+        nul, prs = tii_synth_set([[net] * 12] * 4, [17, 17, 14, 14], [1001, 1083, 1051, 1056])
+        want, ties = tii_oracle_pairs(nul, prs)
+        return nul, prs, want, ties
+    return _tii_cached("ties", make)
+
+
+def check_tii_pairs_ties(d_factory):
+    """equal sums: the winner is the candidate std::min_element meets first in the iteration order of the reference's unordered_map, which
+    differs between a map filled for the first time (cycle 0) and one refilled after clear() (cycle 1)"""
+    nul, prs, want, ties = tii_set_ties()
+    tied = [sum(1 for t in ens for a, cycle in [t] if a >= 2 and cycle == k) for k in (0, 1) for ens in [sum(ties, [])]]
+    assert tied[0] >= 3 and tied[1] >= 3, "reports with a shared minimum per cycle: %s" % tied
+    d = tii_pairs_handle(d_factory, 4, 12)
+    try:
+        got, n = tii_device_pairs(d, nul, prs)
+        for b in range(4):
+            diff = [(g, w, t) for g, w, t in zip(got[b], want[b], ties[b]) if g != w]
+            assert got[b] == want[b], "ensemble %d: (got, want, (candidates at the minimum, cycle)) %s" % (b, diff or (got[b], want[b]))
+    finally:
+        d.close()
+
+
+def tii_set_scaled():
+    """one set of pairs (four transmitters, 15 dB) as it is and times 2^30, 2^-30, 2^-70 (squared magnitudes denormal or zero); the same
+    set with an all-zero NULL symbol, an all-zero PRS, and both, in three of its frames"""
+    def make():
+        net = [(3, 17, 0, 1.0), (11, 40, 37, 0.6), (0, 69, -4, 0.8), (23, 0, 499, 0.7)]
+        nul1, prs1 = tii_synth_pairs([net] * 6, 15, 77)
+        nul = np.stack([nul1 * np.float32(s) for s in (1.0, 2.0 ** 30, 2.0 ** -30, 2.0 ** -70)] + [nul1.copy()])
+        prs = np.stack([prs1 * np.float32(s) for s in (1.0, 2.0 ** 30, 2.0 ** -30, 2.0 ** -70)] + [prs1.copy()])
+        nul[4, 1] = 0; prs[4, 3] = 0; nul[4, 4] = 0; prs[4, 4] = 0
+        assert np.isfinite(nul.view(np.float32)).all() and np.isfinite(prs.view(np.float32)).all()
+        want, ties = tii_oracle_pairs(nul, prs)
+        return nul, prs, want
+    return _tii_cached("scaled", make)
+
+
+def check_tii_pairs_scaled(d_factory):
+    """every decision of k_tii_measure is invariant under a power of two until the squared magnitudes leave the normal float range; there
+    and at all-zero symbols the restatement's result (denormals kept) is the expectation"""
+    nul, prs, want = tii_set_scaled()
+    assert len(want[0]) == 4 and want[1] == want[0] and want[2] == want[0], want[:3]
+    d = tii_pairs_handle(d_factory, 5, 6)
+    try:
+        got, n = tii_device_pairs(d, nul, prs, calls=[2, 4])
+        for b, what in enumerate(("unscaled", "x 2^30", "x 2^-30", "x 2^-70", "zero NULL / zero PRS frames")):
+            assert got[b] == want[b], "%s:\n got  %s\n want %s" % (what, got[b], want[b])
+    finally:
+        d.close()
+
+
+def check_tii_pairs_small_output(d_factory):
+    """dabphy_get_tii with room for fewer measurements than there are: n[b] is the full count, the first max_per_ensemble slots hold the
+    first measurements in the documented order (frame, then comb * 70 + pattern), nothing else of the caller's array is written"""
+    import ctypes as C
+    nul, prs, want = tii_set_scaled()
+    nul = nul[[0, 3, 4]]; prs = prs[[0, 3, 4]]; want = [want[0], want[3], want[4]]
+    nul[1] *= 0; want[1] = []                                          # an ensemble with nothing to report
+    assert len(want[0]) == 4 and sorted(want[0]) == want[0]
+    d = tii_pairs_handle(d_factory, 3, 6)
+    try:
+        d.test_tii_pairs(nul, prs)
+        full, n_full = d.tii()
+        guard = np.frombuffer(bytes([0x5a]) * capi_tii_itemsize(), R.TII_EVENT_DTYPE)[0]
+        buf = np.full(3 * 2 + 3, guard, R.TII_EVENT_DTYPE); n = np.full(3, -1, np.int32)
+        d._chk(d.lib.dabphy_get_tii(d.h, buf.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p), 2))
+        assert n.tolist() == [len(w) for w in want] == n_full.tolist() and n[0] > 2
+        for b in range(3):
+            k = min(len(want[b]), 2)
+            got = [(int(e["frame"]), int(e["comb"]), int(e["pattern"]), int(e["delay_samples"]), float(e["error"])) for e in buf[2 * b:2 * b + k]]
+            assert got == want[b][:k], (b, got, want[b][:k])
+            assert (buf[2 * b + k:2 * b + 2].view(np.uint8) == 0x5a).all(), "ensemble %d: slots behind its %d measurements were written" % (b, k)
+        assert (buf[6:].view(np.uint8) == 0x5a).all(), "dabphy_get_tii wrote behind [n_ensembles][max_per_ensemble]"
+    finally:
+        d.close()
+
+
+def capi_tii_itemsize():
+    return R.TII_EVENT_DTYPE.itemsize

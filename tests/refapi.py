@@ -398,6 +398,23 @@ def orc_tii_run(nulls, prss, want_detect=False):
     return (out, det) if want_detect else out
 
 
+def orc_tii_events(nulls, prss, want_detect=False):
+    """the same restatement, events in the order it makes them (frame, then comb * 70 + pattern ascending: the order include/dabphy.h
+    documents for the device) -> (events, ties): ties[i] = (candidates at the minimum sum, cycle) of event i; want_detect adds the
+    [n][192] detection flags of every pair's carriers"""
+    nulls = np.ascontiguousarray(nulls, np.complex64); prss = np.ascontiguousarray(prss, np.complex64)
+    lib = orc(); lib.orc_tii_state_bytes.restype = C.c_size_t
+    st = np.zeros(lib.orc_tii_state_bytes(), np.uint8); rank = orc_tii_rank()
+    out = []; ties = []; det = np.zeros((len(nulls), 192), np.uint8)
+    for i in range(len(nulls)):
+        ev = np.zeros(16, TII_EVENT_DTYPE); t = np.zeros((16, 2), np.int32)
+        n = lib.orc_tii_frame_ties(_p(st), _p(nulls[i]), _p(prss[i]), _p(rank), _p(ev), 16, _p(det[i]), _p(t))
+        assert n <= 9
+        out += [(i, int(e["comb"]), int(e["pattern"]), int(e["delay_samples"]), float(e["error"])) for e in ev[:n]]
+        ties += [(int(a), int(c)) for a, c in t[:n]]
+    return (out, ties, det) if want_detect else (out, ties)
+
+
 def ref_tii_run(nulls, prss):
     """the reference's TIIDecoder class over the same pairs"""
     nulls = np.ascontiguousarray(nulls, np.complex64); prss = np.ascontiguousarray(prss, np.complex64)

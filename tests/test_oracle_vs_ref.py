@@ -1,6 +1,8 @@
 """Pins the oracle (oracle/dabphy_oracle.c) to the REAL reference compiled by oracle/Makefile into oracle/_ref.
 Skipped where the prebuilt reference libraries are absent (they are built in the authoring container, where
 /root/reference exists, and travel to the GPU box as binaries); tests/test_golden.py covers that case."""
+import os
+
 import numpy as np
 import pytest
 
@@ -265,6 +267,36 @@ def test_tii_decoder_noise_and_garbage(oracle_built):
     eo, det = R.orc_tii_run(nul2, prs2, want_detect=True)
     assert eo == R.ref_tii_run(nul2, prs2) and len(eo) >= 2
     assert det[3].sum() > 100 and det[2].sum() == 0
+
+
+def _tii_set(name):
+    """the synthesised (NULL, PRS) sets of the device's pair-level TII cases (parity_cases.check_tii_pairs_*) -> NULL, PRS, valid, oracle events"""
+    if name in ("every_comb_and_pattern", "every_pair"):
+        nets, nul, prs, want = P.tii_set_every_pair(name == "every_pair")
+        return nul, prs, None, want
+    if name == "likely_limit_and_ghosts":
+        nul, prs, valid, want, reports = P.tii_set_likely_limit()
+        return nul, prs, valid, want
+    if name == "forty_pairs":
+        nul, prs, want, likely = P.tii_set_slot_exhaustion()
+        return nul, prs, None, want
+    nul, prs, want = (P.tii_set_ties()[:3] if name == "ties" else P.tii_set_scaled())
+    return nul, prs, None, want
+
+
+@pytest.mark.parametrize("name", ["every_comb_and_pattern", "every_pair", "likely_limit_and_ghosts", "forty_pairs", "ties", "scaled"])
+def test_tii_pair_sets_equal_reference(oracle_built, name):
+    """the expectations of the pair-level TII cases rest on the real TIIDecoder: fed the same pairs (the demodulated frames only) it makes
+    the restatement's measurements -- all 1 680 comb/pattern pairs, 9 against 10 likely pairs, ghost pairs, shared minima in both
+    generations of the map, magnitudes down to denormal squares, and 40 pairs at once (its map is unbounded)"""
+    if name == "every_pair" and not os.environ.get("DABPHY_FULL_CPU_SUITE"):
+        pytest.skip("every comb and every pattern run by default; DABPHY_FULL_CPU_SUITE=1 runs all 1 680 pairs through the reference")
+    nul, prs, valid, want = _tii_set(name)
+    for b in range(len(nul)):
+        idx = np.arange(nul.shape[1]) if valid is None else np.flatnonzero(valid[b] == 1)
+        er = [(int(idx[e[0]]),) + e[1:] for e in R.ref_tii_run(nul[b][idx], prs[b][idx])]
+        assert er == sorted(want[b]), "ensemble %d:\n reference   %s\n restatement %s" % (b, er, sorted(want[b]))
+    assert sum(len(w) for w in want) >= 4
 
 
 @pytest.mark.parametrize("method", [0, 1])

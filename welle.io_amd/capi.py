@@ -226,6 +226,21 @@ class DabPhy:
         self._chk(self.lib.dabphy_get_tii(self.h, _p(ev), _p(n), m))
         return [ev[b, :min(int(n[b]), m)].copy() for b in range(B)], n
 
+    def test_tii_pairs(self, null, prs, valid=None):
+        """dabphy_test_tii_pairs: the TII kernels over (NULL [B][F][2656], PRS [B][F][2048]) pairs; valid [B][F] (default: all 1).
+        tii() then returns this call's measurements"""
+        B = self.cfg.n_ensembles
+        null = np.ascontiguousarray(null, np.complex64).reshape(B, -1, 2656); F = null.shape[1]
+        prs = np.ascontiguousarray(prs, np.complex64).reshape(B, F, 2048)
+        valid = np.ones((B, F), np.int32) if valid is None else np.ascontiguousarray(valid, np.int32).reshape(B, F)
+        self._chk(self.lib.dabphy_test_tii_pairs(self.h, _p(null), _p(prs), _p(valid), B, F))
+
+    def test_tii_dropped(self):
+        """dabphy_test_tii_dropped: measurements per ensemble that found all 32 slots taken"""
+        n = np.zeros(self.cfg.n_ensembles, np.int32)
+        self._chk(self.lib.dabphy_test_tii_dropped(self.h, _p(n)))
+        return n
+
     def selftest_unit_twiddle(self):
         c = (C.c_uint64 * 2)()
         self._chk(self.lib.dabphy_selftest_unit_twiddle(self.h, c))

@@ -435,13 +435,11 @@ int dabphy_set_tii(dabphy_handle* h, int32_t on)
         if ((r = ensure(h, h->tii_rot, T.rot.size() * sizeof(cf32)))) return r;
         if ((r = ensure(h, h->tii_rank, sizeof T.rank))) return r;
         if ((r = ensure(h, h->tii_pat, sizeof T.pattern))) return r;
-        if ((r = ensure(h, h->tii_state, (size_t)B * TII_SLOTS * sizeof(TiiSlot)))) return r;
-        if ((r = ensure(h, h->tii_ovf, (size_t)B * sizeof(int32_t)))) return r;
+        if ((r = ensure(h, h->tii_state, tii_state_bytes(B)))) return r;
         HIPCHK(h, hipMemcpyAsync(h->tii_rot.p, T.rot.data(), T.rot.size() * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->tii_rank.p, T.rank, sizeof T.rank, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->tii_pat.p, T.pattern, sizeof T.pattern, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemsetAsync(h->tii_state.p, 0, h->tii_state.cap, h->stream));
-        HIPCHK(h, hipMemsetAsync(h->tii_ovf.p, 0, h->tii_ovf.cap, h->stream));
         if ((r = sync(h))) return r;
     }
     h->tii_on = on != 0;
@@ -451,7 +449,7 @@ int dabphy_set_tii(dabphy_handle* h, int32_t on)
 int dabphy_get_tii(dabphy_handle* h, dabphy_tii_measurement* out, int32_t* n, uint32_t max_per_ensemble)
 {
     DeviceBind dev_(h);
-    if (!h || !n || (!out && max_per_ensemble) || !h->last_frames) return DABPHY_ERR_INVALID;
+    if (!h || !n || (!out && max_per_ensemble) || (!h->last_frames && !h->tii_ran)) return DABPHY_ERR_INVALID;
     const uint32_t B = h->cfg.n_ensembles;
     if (!h->tii_ran) { for (uint32_t b = 0; b < B; b++) n[b] = 0; return DABPHY_OK; }
     static_assert(sizeof(dabphy_tii_measurement) == sizeof(TiiEvent), "dabphy_tii_measurement layout");
@@ -464,6 +462,51 @@ int dabphy_get_tii(dabphy_handle* h, dabphy_tii_measurement* out, int32_t* n, ui
         if (k) memcpy(out + (size_t)b * max_per_ensemble, ev.data() + (size_t)b * h->tii_max_events, k * sizeof(TiiEvent));
     }
     return DABPHY_OK;
+}
+
+// include/dabphy_test.h: launch_tii as dabphy_process queues it, over frames built from the caller's (NULL, PRS) pairs
+int dabphy_test_tii_pairs(dabphy_handle* h, const float* null, const float* prs, const int32_t* valid, uint32_t n_ens, uint32_t n_frames)
+{
+    DeviceBind dev_(h);
+    if (!h || !null || !prs || !valid || n_ens != h->cfg.n_ensembles || n_frames == 0 || n_frames > h->cfg.max_frames) return DABPHY_ERR_INVALID;
+    if (!h->tii_on || !h->tii_rot.p) { h->err = "dabphy_test_tii_pairs: the TII side path is off (dabphy_set_tii)"; return DABPHY_ERR_INVALID; }
+    const uint32_t B = n_ens, F = n_frames;
+    // Frame f of an ensemble: PRS at sample f * SLOT, NULL symbol NULL_AT = T_u + 75 T_s samples behind it as in a transmission frame.
+    // The kernels address samples modulo the ring: with a ring that divides 75 T_s the NULL symbol lands right behind its PRS, and a
+    // frame takes T_u + T_null samples instead of T_F; deeper batches than such a ring holds get whole frames.
+    constexpr int64_t SLOT = T_U + T_NULL, NULL_AT = T_U + 75LL * T_S;
+    int64_t ring = 0, pitch = SLOT;
+    for (int q = 3; q >= 1 && !ring; q--) if ((NULL_AT - T_U) % q == 0 && (NULL_AT - T_U) / q >= (int64_t)F * SLOT) ring = (NULL_AT - T_U) / q;
+    if (!ring) { pitch = T_F; ring = (int64_t)F * T_F; }
+    std::vector<cf32> iq((size_t)B * ring);                           // (zeros between the frames)
+    std::vector<FrameDesc> d((size_t)B * F);
+    for (uint32_t b = 0; b < B; b++)
+        for (uint32_t f = 0; f < F; f++) {
+            const size_t i = (size_t)b * F + f;
+            cf32* const at = iq.data() + (size_t)b * ring;
+            memcpy(at + f * pitch, prs + 2 * i * T_U, T_U * sizeof(cf32));
+            for (int64_t k = 0; k < T_NULL; k++) memcpy(at + (f * pitch + NULL_AT + k) % ring, null + 2 * (i * T_NULL + k), sizeof(cf32));
+            FrameDesc& e = d[i];
+            memset(&e, 0, sizeof e);                                  // L0 = f_prs = null_L = null_f = 0: the oscillator stays at 1 + 0j
+            e.pos = f * pitch; e.frame_no = f; e.valid = valid[i];
+        }
+    int r;
+    if ((r = ensure(h, h->iq, iq.size() * sizeof(cf32)))) return r;
+    if ((r = ensure(h, h->desc, d.size() * sizeof(FrameDesc)))) return r;
+    if ((r = tii_reserve(h, B, F))) return r;
+    HIPCHK(h, hipMemcpyAsync(h->iq.p, iq.data(), iq.size() * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->desc.p, d.data(), d.size() * sizeof(FrameDesc), hipMemcpyHostToDevice, h->stream));
+    launch_tii(tii_args(h, h->iq.as<cf32>(), (size_t)ring, ring, h->desc.as<FrameDesc>(), B, F), h->stream);
+    h->tii_ran = true;
+    return sync(h);
+}
+
+int dabphy_test_tii_dropped(dabphy_handle* h, int32_t* per_ensemble)
+{
+    DeviceBind dev_(h);
+    if (!h || !per_ensemble || !h->tii_state.p) return DABPHY_ERR_INVALID;
+    HIPCHK(h, hipMemcpyAsync(per_ensemble, tii_dropped(h), (size_t)h->cfg.n_ensembles * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    return sync(h);
 }
 
 } // extern "C"

@@ -218,7 +218,7 @@ struct dabphy_handle {
         bool polled = false;                                         // a fetch has been made since the last dabphy_process: the next one runs the waiting pass at once (the end of a stream)
         hipEvent_t done = nullptr;                                   // behind the deferred pass on the auxiliary stream (created with the first one)
     } sf;
-    DevBuf tii_rot, tii_rank, tii_pat, tii_err, tii_likely, tii_state, tii_events, tii_nev, tii_ovf;
+    DevBuf tii_rot, tii_rank, tii_pat, tii_err, tii_likely, tii_state, tii_events, tii_nev;     // (tii_state: [B][TII_SLOTS] sums, then [B] dropped-measurement counters -- one carried block)
     uint32_t tii_max_events = 0;
 };
 
@@ -356,6 +356,30 @@ inline int copy_carried(dabphy_handle* h, void* dst, const void* src, size_t byt
 {
     if (dst && src) HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
     return 0;
+}
+
+// TII: the carried block is the slots of every ensemble followed by its dropped-measurement counters (they are saved, put back and
+// reset with the sums); per-batch scratch and the argument block of launch_tii, for dabphy_process and dabphy_test_tii_pairs alike
+inline size_t tii_state_bytes(uint32_t B) { return (size_t)B * TII_SLOTS * sizeof(TiiSlot) + (size_t)B * sizeof(int32_t); }
+inline int32_t* tii_dropped(const dabphy_handle* h) { return reinterpret_cast<int32_t*>(h->tii_state.as<TiiSlot>() + (size_t)h->cfg.n_ensembles * TII_SLOTS); }
+inline int tii_reserve(dabphy_handle* h, uint32_t B, uint32_t F)
+{
+    int r;
+    if ((r = ensure(h, h->tii_err, (size_t)B * F * TII_MAX_LIKELY * TII_NERR * sizeof(float)))) return r;
+    if ((r = ensure(h, h->tii_likely, (size_t)B * F * (1 + TII_MAX_LIKELY) * sizeof(int32_t)))) return r;
+    if ((r = ensure(h, h->tii_events, (size_t)B * TII_MAX_LIKELY * h->cfg.max_frames * sizeof(TiiEvent)))) return r;
+    return ensure(h, h->tii_nev, (size_t)B * sizeof(int32_t));
+}
+inline TiiArgs tii_args(dabphy_handle* h, const cf32* iq, size_t iq_stride, int64_t ring, const FrameDesc* desc, uint32_t B, uint32_t F)
+{
+    h->tii_max_events = TII_MAX_LIKELY * h->cfg.max_frames;
+    TiiArgs ta{};
+    ta.tab = h->tab; ta.iq = iq; ta.iq_stride = iq_stride; ta.ring = ring; ta.desc = desc; ta.n_ens = (int)B; ta.n_frames = (int)F;
+    ta.rot = h->tii_rot.as<cf32>(); ta.rank = h->tii_rank.as<int32_t>(); ta.pattern = h->tii_pat.as<uint8_t>();
+    ta.abs_err = h->tii_err.as<float>(); ta.likely = h->tii_likely.as<int32_t>(); ta.state = h->tii_state.as<TiiSlot>();
+    ta.events = h->tii_events.as<TiiEvent>(); ta.n_events = h->tii_nev.as<int32_t>(); ta.max_events = (int)h->tii_max_events;
+    ta.overflow = tii_dropped(h);
+    return ta;
 }
 
 inline int sync(dabphy_handle* h)

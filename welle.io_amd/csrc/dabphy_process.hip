@@ -86,12 +86,7 @@ static int reserve_batch(dabphy_handle* h, const Batch& b)
     if ((r = ensure(h, h->s_fib, std::max((size_t)B * F * 384, (size_t)fic.n_groups * 64 * 96)))) return r;      // the class output holds whole groups of 64 codewords
     if ((r = ensure(h, h->s_ok, (size_t)B * F * 12))) return r;
     if (h->cfg.want_constellation && (r = ensure(h, h->s_con, (size_t)B * F * 1200 * sizeof(cf32)))) return r;
-    if (h->tii_on) {
-        if ((r = ensure(h, h->tii_err, (size_t)B * F * TII_MAX_LIKELY * TII_NERR * sizeof(float)))) return r;
-        if ((r = ensure(h, h->tii_likely, (size_t)B * F * (1 + TII_MAX_LIKELY) * sizeof(int32_t)))) return r;
-        if ((r = ensure(h, h->tii_events, (size_t)B * TII_MAX_LIKELY * h->cfg.max_frames * sizeof(TiiEvent)))) return r;
-        if ((r = ensure(h, h->tii_nev, (size_t)B * sizeof(int32_t)))) return r;
-    }
+    if (h->tii_on && (r = tii_reserve(h, B, F))) return r;
     for (auto& cls : h->classes) {
         const size_t n_groups = ((size_t)4 * F * cls.pairs.size() + 63) / 64;
         if ((r = ensure(h, cls.out, n_groups * 64 * (cls.prot.nbits / 8)))) return r;
@@ -242,14 +237,7 @@ static int queue_aux_work(dabphy_handle* h, const Batch& b)
     h->tii_ran = false;
     if (h->tii_on) {
         // TII side path (ofdm-processor.cpp:462-466 -> TIIDecoder): needs only the samples and the frame descriptors
-        h->tii_max_events = TII_MAX_LIKELY * h->cfg.max_frames;
-        TiiArgs ta{};
-        ta.tab = h->tab; ta.iq = h->s_iq; ta.iq_stride = h->s_stride; ta.ring = (int64_t)h->s_ring; ta.desc = b.d_desc; ta.n_ens = (int)B; ta.n_frames = (int)F;
-        ta.rot = h->tii_rot.as<cf32>(); ta.rank = h->tii_rank.as<int32_t>(); ta.pattern = h->tii_pat.as<uint8_t>();
-        ta.abs_err = h->tii_err.as<float>(); ta.likely = h->tii_likely.as<int32_t>(); ta.state = h->tii_state.as<TiiSlot>();
-        ta.events = h->tii_events.as<TiiEvent>(); ta.n_events = h->tii_nev.as<int32_t>(); ta.max_events = (int)h->tii_max_events;
-        ta.overflow = h->tii_ovf.as<int32_t>();
-        launch_tii(ta, fs);
+        launch_tii(tii_args(h, h->s_iq, h->s_stride, (int64_t)h->s_ring, b.d_desc, B, F), fs);
         h->tii_ran = true;
     }
     // the host's copies of the descriptors and SNR reports leave here, beside the decoder, instead of behind the step's last kernel
