@@ -59,7 +59,7 @@ typedef enum {
 uint32_t dabphy_abi_version(void);
 typedef enum { DABPHY_STRUCT_CONFIG = 0, DABPHY_STRUCT_FRAME_INFO = 1, DABPHY_STRUCT_SF_EVENT = 2, DABPHY_STRUCT_SUBCHANNEL = 3,
                DABPHY_STRUCT_PROTECTION = 4, DABPHY_STRUCT_TII_MEASUREMENT = 5, DABPHY_STRUCT_MSC_DESC = 6,
-               DABPHY_STRUCT_MP2_EVENT = 7 } dabphy_struct_id;
+               DABPHY_STRUCT_MP2_EVENT = 7, DABPHY_STRUCT_AU_SERVICE = 8, DABPHY_STRUCT_AU_DESC = 9 } dabphy_struct_id;
 size_t dabphy_struct_size(int32_t which);      /* 0 for an unknown id */
 
 /* RadioReceiverOptions (src/backend/radio-receiver-options.h:66-84) + batch geometry */
@@ -359,7 +359,8 @@ int dabphy_get_msc_ensemble(dabphy_handle* h, uint32_t ensemble, uint32_t subch_
  *   dabphy_msc_drain_begin       queue the copies on a stream of their own and return at once: the NEXT dabphy_process may be called while
  *                                they are in flight (the class outputs are first copied to a staging area in HBM -- tens of microseconds on
  *                                the device -- so that no decoder ever waits for the host link); `desc` is complete on return, `buf` when
- *   dabphy_msc_drain_wait        returns (also called by dabphy_destroy / dabphy_reset and before the sub-channel lists are re-applied).
+ *   dabphy_msc_drain_wait        returns (dabphy_destroy, dabphy_reset and a dabphy_process that re-applies the sub-channel lists wait for a
+ *                                drain in flight themselves: `buf` must stay valid until one of them or dabphy_msc_drain_wait has returned).
  * DABPHY_ERR_INVALID when a capacity is too small (nothing is queued then). */
 typedef struct {
     uint32_t ensemble, subch_index;      /* position in that ensemble's list (dabphy_set_subchannels[_ensemble]) */
@@ -494,6 +495,67 @@ int dabphy_set_auto_mp2(dabphy_handle* h, int32_t on);
  *   frame_errors [n_streams][n_frames], first_unverified [n_streams]; event.frame = index of the logical frame. */
 int dabphy_mp2_check(dabphy_handle* h, const uint8_t* frames, uint32_t n_streams, uint32_t n_frames, uint32_t frame_len,
                      dabphy_mp2_event* events, int32_t cap, int32_t* n_events, int32_t* frame_errors, int32_t* first_unverified);
+
+/* ---- Bulk access-unit drain: the audio of EVERY DAB+ service of every ensemble, in one copy per batch -----------------------------------
+ * What a consumer gets behind SuperframeFilter::Feed (dabplus_decoder.cpp:121-138): every access unit that passed its CRC, CRC stripped,
+ *   DABPHY_AU_RAW    as AACDecoder::DecodeFrame receives it, or
+ *   DABPHY_AU_LOAS   wrapped into one LATM/LOAS AudioSyncStream frame exactly as ProcessUntouchedStream builds it (:257-312): the frames of
+ *                    a service, appended to a file as they come, are a playable .aac stream that carries its own configuration.
+ * dabphy_set_au_drain switches a pack pass on (format != DABPHY_AU_OFF) that runs on the device directly behind every all-sub-channel
+ * filter pass queued after the call -- dabphy_superframes_stats, dabphy_set_auto_superframes 1 and 2 alike; MP2 positions stay out as
+ * they do there -- and leaves the access units of every service back to back in a staging buffer in HBM.  While the drain is off
+ * nothing is launched and nothing is allocated.
+ *   Which batch.  The drain refers to the filter pass that ran LAST -- the batch whose totals dabphy_superframes_stats returns: in mode 1
+ *     the batch just processed; in mode 2 the batch BEFORE the last dabphy_process (nothing after the first one); at the end of a stream a
+ *     second dabphy_superframes_stats without a dabphy_process in between runs the waiting pass, and the drain then returns that batch.
+ *   One drain per pass.  A second dabphy_au_drain_begin on the same pass, or one before any pass has run with the drain on, returns
+ *     DABPHY_ERR_STATE and queues nothing.  dabphy_au_batch_size describes the pass queued LAST, drained or not: it answers from the
+ *     first pass with the drain on until the drain is switched off (DABPHY_ERR_STATE before and after), and changes only with the
+ *     sub-channel lists or n_frames -- one query per geometry.
+ *   services [n]   one record per DAB+ (ensemble, list position), ordered by ensemble, then by position, like dabphy_msc_desc: the bytes
+ *                  buf[offset .. offset + bytes) are that service's access units of the batch, back to back (LOAS: its stream for this
+ *                  batch); n_superframes = synchronised superframes, n_aus = access units stored, n_failed = access units that failed
+ *                  their CRC (skipped, as the reference `continue`s); a service without a synchronised superframe has n_aus = 0.
+ *   aus            access-unit records, grouped by service: aus[first_au .. first_au + n_aus) in order; records outside those ranges are
+ *                  undefined.  cif = the logical frame that completed the superframe (dabphy_sf_event.cif), au_index = its number in the
+ *                  superframe, format = sf[2], offset / length = where its bytes lie in buf and how many (LOAS: the whole frame): they
+ *                  tile the service's extent without gaps.  aus == NULL skips the table and its copy (a LOAS consumer does not need it).
+ *   buf            one region per protection class, 256-byte aligned; inside it one fixed reservation per (ensemble, sub-channel) pair,
+ *                  sized by a bound from the bit rate and the batch depth (the payload of 4 * n_frames / 5 + 1 superframes plus the
+ *                  worst LOAS overhead).  dabphy_au_batch_size reports the sum, the number of service records and the number of
+ *                  access-unit records `aus` must hold.  The copy is one device-to-host transfer of the staging buffer, in pieces like the
+ *                  MSC drain's: at PCIe rate into memory from dabphy_host_alloc.  Bytes of a reservation behind `bytes` are undefined.
+ *   When.  The tables are written by the DEVICE: services, aus and buf are complete when dabphy_au_drain_wait returns (n_services /
+ *     n_aus = records of each table, either may be NULL), not on return from dabphy_au_drain_begin, and must stay valid until then.
+ *     dabphy_au_drain_begin returns at once: the next dabphy_process may be called while the copies are in flight; the pack pass it queues
+ *     waits ON THE DEVICE for them before it overwrites the staging buffer.  dabphy_get_au_batch = begin + wait.
+ *   A capacity that is too small returns DABPHY_ERR_INVALID and queues nothing.
+ *   The tables follow the classes as they were when the pass was QUEUED: in mode 2 a dabphy_process with a changed sub-channel list first
+ *     runs the waiting pass under the old list, then rebuilds the classes; the drain after it returns that batch under the old list.
+ *   An access-unit drain and an MSC drain may be in flight together (they share the copy stream, each has its own staging buffer).
+ *   dabphy_destroy, dabphy_reset and a change of format wait for a drain in flight; dabphy_reset and a change of format drop a pass that
+ *   has not been drained. */
+#define DABPHY_AU_OFF 0
+#define DABPHY_AU_RAW 1
+#define DABPHY_AU_LOAS 2
+int dabphy_set_au_drain(dabphy_handle* h, int32_t format);
+typedef struct {
+    uint32_t ensemble, subch_index, subch_id;      /* position in that ensemble's list; SubChId as given in the list */
+    int32_t n_superframes, n_aus, n_failed;
+    uint32_t first_au, pad_;                       /* index of its first record in aus */
+    uint64_t offset, bytes;                        /* its extent in buf */
+} dabphy_au_service;
+typedef struct {
+    int32_t cif; uint8_t au_index, format, pad_[2];
+    uint32_t length, pad2_;
+    uint64_t offset;
+} dabphy_au_desc;
+int dabphy_au_batch_size(dabphy_handle* h, size_t* buf_bytes, uint32_t* n_services, uint32_t* n_aus_capacity);
+int dabphy_au_drain_begin(dabphy_handle* h, dabphy_au_service* services, uint32_t services_capacity,
+                          dabphy_au_desc* aus /* may be NULL */, uint32_t aus_capacity, uint8_t* buf, size_t buf_capacity);
+int dabphy_au_drain_wait(dabphy_handle* h, uint32_t* n_services, uint32_t* n_aus);
+int dabphy_get_au_batch(dabphy_handle* h, dabphy_au_service* services, uint32_t services_capacity, dabphy_au_desc* aus, uint32_t aus_capacity,
+                        uint8_t* buf, size_t buf_capacity, uint32_t* n_services, uint32_t* n_aus);
 
 /* ---- TIIDecoder (tii-decoder.cpp:189-383), fed by OFDMProcessor::run with the PRS and the trailing NULL symbol of every
  * frame (ofdm-processor.cpp:381-386,462-466) when RadioReceiverOptions::decodeTII is set (radio-receiver-options.h:75; welle-cli

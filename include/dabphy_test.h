@@ -73,6 +73,16 @@ int dabphy_test_tii_pairs(dabphy_handle* h, const float* null, const float* prs,
  * comb/pattern pairs, since dabphy_set_tii switched the side path on for the first time or the last dabphy_reset. */
 int dabphy_test_tii_dropped(dabphy_handle* h, int32_t* per_ensemble);
 
+/* Unit entry of the access-unit pack pass (k_au_pack, the launch behind every filter pass while dabphy_set_au_drain is on) on host-supplied
+ * corrected superframes and their events, treated as ONE service: sf [n_sf][120 * s_per_sf], events [n_events] as the filter writes them
+ * (sf_slot = index into sf, au_crc_ok as it stands: no CRC is checked here), format = DABPHY_AU_RAW / DABPHY_AU_LOAS.  out [out_capacity]
+ * receives the service's whole reservation (out_capacity bytes, zeros behind service->bytes; the first access unit that does not fit
+ * the reservation or the aus_capacity records is left out with everything behind it: n_aus and bytes count what was stored), aus [aus_capacity] its records with offsets relative to out, *service its totals.  The handle's drain is not touched. */
+int dabphy_test_au_pack(dabphy_handle* h, const uint8_t* sf, const dabphy_sf_event* events, uint32_t n_events, uint32_t n_sf, uint32_t s_per_sf,
+                        int32_t format, uint8_t* out, size_t out_capacity, dabphy_au_desc* aus, uint32_t aus_capacity, dabphy_au_service* service);
+/* dabphy_get_au_ms: device time of the last pack pass queued with dabphy_set_profiling on; 0 if none */
+int dabphy_get_au_ms(dabphy_handle* h, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,10 @@ MP2_EVENT_DTYPE = np.dtype([("frame", "<i4"), ("header", "<u4"), ("offset", "<i8
                             ("fpad", "u1", 2), ("pad_", "u1", 3)])      # dabphy_mp2_event
 AUDIO_DABPLUS, AUDIO_MP2 = 0, 1                                           # dabphy_set_audio_kinds_ensemble
 MSC_DESC_DTYPE = np.dtype([("ensemble", "<u4"), ("subch_index", "<u4"), ("row_bytes", "<u4"), ("first_valid", "<i4"), ("n_rows", "<i4"), ("subch_id", "<u4"), ("offset", "<u8")])
+AU_OFF, AU_RAW, AU_LOAS = 0, 1, 2                                           # dabphy_set_au_drain
+AU_SERVICE_DTYPE = np.dtype([("ensemble", "<u4"), ("subch_index", "<u4"), ("subch_id", "<u4"), ("n_superframes", "<i4"), ("n_aus", "<i4"), ("n_failed", "<i4"),
+                             ("first_au", "<u4"), ("pad_", "<u4"), ("offset", "<u8"), ("bytes", "<u8")])      # dabphy_au_service
+AU_DESC_DTYPE = np.dtype([("cif", "<i4"), ("au_index", "u1"), ("format", "u1"), ("pad_", "u1", 2), ("length", "<u4"), ("pad2_", "<u4"), ("offset", "<u8")])      # dabphy_au_desc
 
 
 class DabPhyError(RuntimeError):
@@ -346,6 +350,65 @@ class DabPhy:
         buf, desc = self.msc_drain_begin(buf, desc)
         self.msc_drain_wait()
         return buf, desc
+
+    # ---- bulk access-unit drain
+    def set_au_drain(self, fmt):
+        """AU_OFF / AU_RAW / AU_LOAS for the filter passes queued from now on (dabphy_set_au_drain)"""
+        self._chk(self.lib.dabphy_set_au_drain(self.h, int(fmt)))
+
+    def au_batch_size(self):
+        """(bytes, service records, access-unit records) a drain of the filter pass that ran last needs (dabphy_au_batch_size)"""
+        nb = C.c_size_t(0); ns = C.c_uint32(0); na = C.c_uint32(0)
+        self._chk(self.lib.dabphy_au_batch_size(self.h, C.byref(nb), C.byref(ns), C.byref(na)))
+        return nb.value, ns.value, na.value
+
+    def au_drain_begin(self, buf=None, services=None, aus=True):
+        """dabphy_au_drain_begin: queue the drain of the filter pass that ran last and return (buf, services, aus) at once -- all three are
+        complete only when au_drain_wait() has returned.  aus: True = allocate the access-unit table, None / False = skip it, or an array"""
+        if buf is None or services is None or aus is True:             # (every array given: no size query stands in front of the entry)
+            nb, ns, na = self.au_batch_size()
+        if buf is None:
+            buf = np.zeros(max(nb, 1), np.uint8)
+        if services is None:
+            services = np.zeros(max(ns, 1), AU_SERVICE_DTYPE)
+        if aus is True:
+            aus = np.zeros(max(na, 1), AU_DESC_DTYPE)
+        elif aus is False:
+            aus = None
+        self._chk(self.lib.dabphy_au_drain_begin(self.h, _p(services), C.c_uint32(len(services)), _p(aus) if aus is not None else None,
+                                                 C.c_uint32(len(aus) if aus is not None else 0), _p(buf), C.c_size_t(buf.nbytes)))
+        self._au_out = (buf, services, aus)
+        return self._au_out
+
+    def au_drain_wait(self):
+        """-> (buf, services [n], aus or None): service k's bytes = buf[offset : offset + bytes], its records aus[first_au : first_au + n_aus]"""
+        ns = C.c_uint32(0); na = C.c_uint32(0)
+        self._chk(self.lib.dabphy_au_drain_wait(self.h, C.byref(ns), C.byref(na)))
+        buf, services, aus = self._au_out
+        return buf, services[:ns.value], (aus[:na.value] if aus is not None else None)
+
+    def au_batch(self, buf=None, services=None, aus=True):
+        """dabphy_get_au_batch: begin + wait"""
+        self.au_drain_begin(buf, services, aus)
+        return self.au_drain_wait()
+
+    def au_ms(self):
+        """device time of the last pack pass queued with profiling on"""
+        ms = C.c_float(0)
+        self._chk(self.lib.dabphy_get_au_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def test_au_pack(self, sf, events, s_per_sf, fmt, out_capacity=None):
+        """unit entry (dabphy_test_au_pack): corrected superframes sf [n_sf][120 * s_per_sf] and their events as ONE service ->
+        (out [out_capacity], aus [n_aus] of AU_DESC_DTYPE, service record)"""
+        sf = np.ascontiguousarray(sf, np.uint8).reshape(-1, 120 * s_per_sf)
+        ev = np.ascontiguousarray(events, SF_EVENT_DTYPE)
+        n_sf = sf.shape[0]
+        cap = n_sf * (120 * s_per_sf + 128) if out_capacity is None else out_capacity
+        out = np.full(max(cap, 1), 0xA5, np.uint8); aus = np.zeros(max(6 * n_sf, 1), AU_DESC_DTYPE); svc = np.zeros(1, AU_SERVICE_DTYPE)
+        self._chk(self.lib.dabphy_test_au_pack(self.h, _p(sf), _p(ev), C.c_uint32(len(ev)), C.c_uint32(n_sf), C.c_uint32(s_per_sf), C.c_int32(int(fmt)),
+                                               _p(out), C.c_size_t(cap), _p(aus), C.c_uint32(len(aus)), _p(svc)))
+        return out[:cap], aus[:int(svc[0]["n_aus"])], svc[0]
 
     def superframes_ensemble(self, ensemble, idx, bitrate):
         """-> (events [4F], n_events, corrected superframes [n_slots][120*bitrate/8]) of one ensemble's sub-channel idx"""

@@ -17,6 +17,8 @@ size_t dabphy_struct_size(int32_t which)
         case DABPHY_STRUCT_TII_MEASUREMENT: return sizeof(dabphy_tii_measurement);
         case DABPHY_STRUCT_MSC_DESC: return sizeof(dabphy_msc_desc);
         case DABPHY_STRUCT_MP2_EVENT: return sizeof(dabphy_mp2_event);
+        case DABPHY_STRUCT_AU_SERVICE: return sizeof(dabphy_au_service);
+        case DABPHY_STRUCT_AU_DESC: return sizeof(dabphy_au_desc);
     }
     return 0;
 }

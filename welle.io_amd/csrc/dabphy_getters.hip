@@ -219,6 +219,22 @@ int drain_wait(dabphy_handle* h)
     return DABPHY_OK;
 }
 
+// The stream the bulk drains (MSC bytes here, access units in dabphy_au.hip) copy on: created with the first drain, shared by both.
+int drain_stream_ready(dabphy_handle* h)
+{
+    int r;
+    if (h->drain_stream) return DABPHY_OK;
+    // Which stream.  The runtime multiplexes a process's streams onto a few hardware queues, and a drain on a stream of its own -- the
+    // handle's sixth -- landed on the main stream's queue on some boxes: 13.0-13.8 ms per step with the drain against 10.0 without
+    // (tools/probe_streams.py, profiles/r06_step_variants.txt).  On the ingest stream, idle whenever the samples are resident in HBM,
+    // it overlaps completely (10.07 ms).  A handle that is fed through dabphy_stream_write_raw_async keeps that stream for its
+    // host-to-device transfers and drains on one of its own.
+    if (h->s_enqueued == 0 && !(h->stream_layout & 8)) h->drain_stream = h->copy_stream;
+    else if ((r = new_stream(h, &h->drain_stream))) return r;
+    if ((r = new_event(h, &h->ev_drain_done)) || (r = new_event(h, &h->ev_drain_staged))) return r;
+    return DABPHY_OK;
+}
+
 int dabphy_msc_batch_size(dabphy_handle* h, size_t* buf_bytes, uint32_t* n_desc)
 {
     if (!h || !h->last_frames) return DABPHY_ERR_INVALID;
@@ -240,16 +256,7 @@ int dabphy_msc_drain_begin(dabphy_handle* h, dabphy_msc_desc* desc, uint32_t des
     if (n > desc_capacity || total > buf_capacity || (total && !buf)) { h->err = "dabphy_msc_drain_begin: buffer or index table too small (dabphy_msc_batch_size)"; return DABPHY_ERR_INVALID; }
     int r;
     if ((r = drain_wait(h))) return r;                      // one drain at a time
-    if (!h->drain_stream) {
-        // Which stream.  The runtime multiplexes a process's streams onto a few hardware queues, and a drain on a stream of its own -- the
-        // handle's sixth -- landed on the main stream's queue on some boxes: 13.0-13.8 ms per step with the drain against 10.0 without
-        // (tools/probe_streams.py, profiles/r06_step_variants.txt).  On the ingest stream, idle whenever the samples are resident in HBM,
-        // it overlaps completely (10.07 ms).  A handle that is fed through dabphy_stream_write_raw_async keeps that stream for its
-        // host-to-device transfers and drains on one of its own.
-        if (h->s_enqueued == 0 && !(h->stream_layout & 8)) h->drain_stream = h->copy_stream;
-        else if ((r = new_stream(h, &h->drain_stream))) return r;
-        if ((r = new_event(h, &h->ev_drain_done)) || (r = new_event(h, &h->ev_drain_staged))) return r;
-    }
+    if ((r = drain_stream_ready(h))) return r;
     // (dabphy_process has returned: the class outputs are final, nothing on the main stream is pending.)  The outputs first go to a
     // staging area in HBM -- a device copy on the main stream, tens of microseconds for a hundred MB, ordered in front of the next batch's
     // kernels like any other work there -- and cross PCIe from the staging area: the next batch's decoders never wait for the host link

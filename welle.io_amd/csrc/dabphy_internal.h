@@ -7,6 +7,7 @@
 //   dabphy_superframes.hip  Reed-Solomon seams and the DAB+ superframe filter
 //   dabphy_mp2.hip          classic DAB (MP2) services: audio kinds, the MP2 frame check and its unit entry
 //   dabphy_getters.hip      everything a caller reads back after a batch, profiling, TII
+//   dabphy_au.hip           the bulk access-unit drain: the pack pass behind the filter (k_au.hip), its tables and its copy to the host
 // Ownership: a device buffer (DevBuf) owns itself and is freed by its destructor; streams, events and page-locked blocks are created
 // through new_stream / new_event / pinned_alloc below and nowhere else, which register them with the handle for dabphy_destroy.
 #pragma once
@@ -218,6 +219,19 @@ struct dabphy_handle {
         bool polled = false;                                         // a fetch has been made since the last dabphy_process: the next one runs the waiting pass at once (the end of a stream)
         hipEvent_t done = nullptr;                                   // behind the deferred pass on the auxiliary stream (created with the first one)
     } sf;
+    // Bulk access-unit drain (dabphy_au.hip; dabphy_set_au_drain): a pack pass behind every all-sub-channel filter pass, drained once.
+    // `last` = layout and services of the pass queued last (the classes as they were THEN: a list change rebuilds them behind a flushed
+    // pass), `flight` = of the pass whose drain is in flight.  Nothing here exists while the drain is off.
+    struct AuDrain {
+        int format = 0;                                              // DABPHY_AU_OFF / _RAW / _LOAS for the passes queued from now on
+        DevBuf stage, svc, tab, src, base; std::vector<int32_t> base_host;   // staging bytes; per-service records; AU records and their sources; first service of every ensemble
+        struct Layout { std::vector<dabphy_au_service> services; std::vector<uint32_t> slot; size_t bytes = 0; uint32_t n_positions = 0, au_cap = 0; int format = 0; } last, flight;   // n_positions: list positions of all ensembles (one record slot each); slot: the service's record on the device
+        bool known = false;                                          // `last` describes a pass (dabphy_au_batch_size answers)
+        bool packed = false, inflight = false;                       // a pass has packed and has not been drained; a drain's copies have been queued and not waited for
+        hipEvent_t ev_packed = nullptr, ev_done = nullptr, ev_time[2] = {nullptr, nullptr}; bool timed = false;
+        AuSvc* h_svc = nullptr; size_t h_svc_cap = 0;                // page-locked landing area of the service records
+        dabphy_au_service* out_services = nullptr; bool out_aus = false;
+    } au;
     DevBuf tii_rot, tii_rank, tii_pat, tii_err, tii_likely, tii_state, tii_events, tii_nev;     // (tii_state: [B][TII_SLOTS] sums, then [B] dropped-measurement counters -- one carried block)
     uint32_t tii_max_events = 0;
 };
@@ -431,6 +445,9 @@ DABPHY_INTERNAL int sp_variant_for(int nsteps);
 DABPHY_INTERNAL bool sp_two_for(const dabphy_handle* h, uint64_t n_cw);
 DABPHY_INTERNAL void launch_sp(const FusedArgs& a, bool two, int lds_variant, hipStream_t s);
 DABPHY_INTERNAL void msc_rows_info(const dabphy_handle* h, uint32_t b, dabphy_handle::PairRef w, int32_t* first_valid, int32_t* n_rows);   // dabphy_getters.hip: rows [first_valid, n_rows) of a pair's class output are the batch's logical frames
+DABPHY_INTERNAL int drain_stream_ready(dabphy_handle* h);                                         // dabphy_getters.hip: the stream both bulk drains copy on, created with the first drain
+DABPHY_INTERNAL int au_pack_pass(dabphy_handle* h, const std::vector<SfSel>& sel, hipStream_t st, uint32_t F);   // dabphy_au.hip: the pack pass behind a filter pass over `sel` (nothing when the drain is off)
+DABPHY_INTERNAL int au_drain_wait(dabphy_handle* h);                                             // ... host waits for an access-unit drain in flight
 DABPHY_INTERNAL int drain_wait(dabphy_handle* h);                                                // dabphy_getters.hip: host waits for a bulk MSC drain in flight
 DABPHY_INTERNAL size_t soft_ens_stride(const dabphy_handle* h);                                   // bytes between the soft-bit ring slices of two ensembles
 }

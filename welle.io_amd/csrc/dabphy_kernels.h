@@ -341,6 +341,23 @@ struct Mp2Args {
     int32_t* stats;                               // optional [B][4]: frames checked, CRC failures, bytes skipped in resync, unverified logical frames
 };
 void launch_mp2(const Mp2Args& a, int n_blocks, hipStream_t s);
+// Access-unit pack pass (k_au.hip) behind the superframe filter: the access units of every synchronised superframe of a pair that passed
+// their CRC, back to back in the pair's region of a staging buffer, raw or as LATM/LOAS frames (dabphy_set_au_drain)
+constexpr int AU_FORMAT_RAW = 1, AU_FORMAT_LOAS = 2;
+struct AuRec {             // = dabphy_au_desc (include/dabphy.h)
+    int32_t cif; uint8_t au_index, format, pad_[2]; uint32_t length, pad2_; uint64_t offset;
+};
+struct AuSvc { int32_t n_superframes, n_aus, n_failed; uint32_t bytes; };     // per service, written for every pair a pass walks
+struct AuArgs {
+    const SfEvent* events; const int32_t* n_events; int n_cif;   // the filter's events of the class [pairs][n_cif], [pairs]
+    const uint8_t* sf; int n_slots, sf_len;                      // ... and its corrected superframes [pairs][n_slots][sf_len]
+    const int32_t* run;                                          // the pairs to walk, one work-group each (nullptr: block i = pair i)
+    const MscPair* pairs; const int32_t* ens_base;               // service of a pair = ens_base[ens] + idx (nullptr: one service, the unit entry)
+    int format;                                                  // AU_FORMAT_RAW / AU_FORMAT_LOAS
+    uint8_t* stage; uint64_t region0, reserve;                   // pair p's bytes from stage + region0 + p * reserve on, at most `reserve`
+    AuSvc* svc; AuRec* aus; uint2* au_src; int au_cap;           // [services], [services][au_cap] records and where their payload lies
+};
+void launch_au_pack(const AuArgs& a, int n_blocks, hipStream_t s);
 void launch_superframe_bucket(const SfBatch& Bt, int bucket, int total_blocks, int n_cif, bool wide_pass, hipStream_t s);
 void launch_rs_superframes(const RsArgs& a, hipStream_t s);
 void launch_rs_msc(const RsMscArgs& a, hipStream_t s);

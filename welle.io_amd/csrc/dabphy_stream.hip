@@ -132,6 +132,8 @@ int dabphy_reset(dabphy_handle* h)
     DeviceBind dev_(h);
     if (!h) return DABPHY_ERR_INVALID;
     int r = reset_synchroniser(h, true); if (r) return r;
+    if ((r = drain_wait(h)) || (r = au_drain_wait(h))) return r;       // bulk drains in flight land first; a pass not drained goes with the stream
+    h->au.packed = false;
     h->desc_sel = 0; h->n_wide_passes = h->n_wide_fallbacks = 0; h->n_replayed_batches = 0;
     h->last_frames = 0; h->last_desc = nullptr;
     if ((r = sf_stream_reset(h))) return r;

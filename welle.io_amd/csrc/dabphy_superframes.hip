@@ -259,7 +259,7 @@ static int launch_superframe_stats(dabphy_handle* h, bool deferred = false)
     if (h->profiling) { hipError_t e = hipEventRecord(h->ev_beg[dabphy_handle::ST_RS], st); (void)e; }
     if ((r = run_superframes(h, sel, h->sf_stats.as<int32_t>(), st, deferred ? h->sf.desc : h->last_desc, deferred ? h->sf.frames : h->last_frames))) return r;
     if (h->profiling) { hipError_t e = hipEventRecord(h->ev_end[dabphy_handle::ST_RS], st); (void)e; h->ev_used[dabphy_handle::ST_RS] = true; }
-    return 0;
+    return au_pack_pass(h, sel, st, deferred ? h->sf.frames : h->last_frames);       // (dabphy_set_au_drain; nothing while it is off)
 }
 // the host waits for a pass in flight: its totals are in h_sf_stats
 static int land_totals(dabphy_handle* h) { if (h->sf.totals == SfPass::IN_FLIGHT) { HIPCHK(h, hipEventSynchronize(h->sf.done)); h->sf.totals = SfPass::LANDED; } return DABPHY_OK; }
