@@ -278,8 +278,7 @@ static int run_lin_decode(dabphy_handle* h, const int8_t* in, size_t in_stride, 
     }
     LinGatherArgs g{}; g.in = h->in8.as<int8_t>(); g.in_stride = in_stride; g.map = d_map; g.c = c;
     launch_lin_gather(g, h->stream);
-    VitArgs v{}; v.c = c; v.prbs_words = h->d_prbs_words;
-    launch_viterbi(v, h->stream);
+    launch_viterbi(vit_args(h, c), h->stream);
     HIPCHK(h, hipMemcpyAsync(out, c.out, (size_t)n_cw * (nbits / 8), hipMemcpyDeviceToHost, h->stream));
     return sync(h);
 }
@@ -319,17 +318,10 @@ int dabphy_fic_decode(dabphy_handle* h, const int8_t* soft, uint32_t n_frames, u
     HIPCHK(h, hipMemcpyAsync(h->desc.p, d.data(), n_frames * sizeof(FrameDesc), hipMemcpyHostToDevice, h->stream));
     FicGatherArgs g{}; g.soft = h->in8.as<int8_t>(); g.soft_ring = (int)n_frames; g.frame_stride = 9216; g.desc = h->desc.as<FrameDesc>();
     g.n_ens = 1; g.n_frames = (int)n_frames; g.map = h->d_fic_map; g.c = c;
-    if (sp_single_ok(h, (uint64_t)n_frames * 4, c.nsteps)) {
-        // (FicHandler::processFicBlock bound per frame: four code words a call)
-        FusedClass fc{}; fc.map = h->d_fic_map; fc.out = c.out; fc.nsteps = c.nsteps; fc.nbits = 768; fc.n_cw = (int32_t)(n_frames * 4); fc.n_pairs = 1; fc.kind = 1; fc.dedisperse = 1;
-        FusedArgs a{}; a.soft = g.soft; a.ens_stride = (size_t)n_frames * 9216; a.soft_ring = (int)n_frames; a.n_ens = 1; a.n_frames = (int)n_frames; a.desc = g.desc; a.fic_frame_stride = 9216;
-        if ((r = sp_single_prepare(h, fc, a, h->stream))) return r;
-        launch_sp(a, h->sp1_two, sp_variant_for(c.nsteps), h->stream);
-    } else {
-        launch_fic_gather(g, h->stream);
-        VitArgs v{}; v.c = c; v.prbs_words = h->d_prbs_words;
-        launch_viterbi(v, h->stream);
-    }
+    // (state-parallel for FicHandler::processFicBlock bound per frame: four code words a call)
+    FicOneClass fic;
+    if ((r = fic_one_prepare(h, fic, g, h->stream))) return r;
+    fic_one_launch(h, fic, 0, h->stream);
     CrcArgs k{}; k.fib = c.out; k.ok = h->ok.as<uint8_t>(); k.state = h->d_dec; k.desc = g.desc; k.n_ens = 1; k.n_frames = (int)n_frames; k.disable_coarse = 1;   // (no synchroniser behind this seam)
     launch_fib_crc(k, h->stream);
     launch_fic_ratio(k, h->stream);
@@ -650,7 +642,7 @@ int dabphy_time_viterbi(dabphy_handle* h, uint32_t nbits, uint32_t n_codewords, 
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     LinGatherArgs g{}; g.in = h->in8.as<int8_t>(); g.in_stride = stride; g.map = nullptr; g.c = c;
-    VitArgs v{}; v.c = c; v.prbs_words = h->d_prbs_words;
+    const VitArgs v = vit_args(h, c);
     ScopedEvent e0, e1, e2;
     HIPCHK(h, e0.create()); HIPCHK(h, e1.create()); HIPCHK(h, e2.create());
     launch_lin_gather(g, h->stream); launch_viterbi(v, h->stream);

@@ -2,15 +2,15 @@
 // launch plan.  No arithmetic of the hot path happens here: the tables restate the depuncturing maps (eep-protection.cpp:32-152,
 // uep-protection.cpp:27-239, fic-handler.cpp:158-191) in terms of the kernel's LDS window ring.
 #include "dabphy_internal.h"
+#include "soft_layout.h"
 
 namespace {
 
 // What every trellis step reads, in terms of a wave's window ring of `rows` rows.  Source byte u of the punctured stream sits in window
-// u >> 4 (slot (u >> 4) & 1), column u & 15 -- and, for an MSC class, map16[u & 15] rows below the lane's row base (the time
-// de-interleaver, dab-audio.cpp:138-143; the FIC has none).  Returns false when the kernel's window schedule cannot follow the map.
+// u >> 4 (slot (u >> 4) & 1), column u & 15 -- and, for an MSC class, layout::tdi_row(u & 15) rows below the lane's row base (the time
+// de-interleaver, soft_layout.h; the FIC has none).  Returns false when the kernel's window schedule cannot follow the map.
 bool step_table(const std::vector<map_t>& m, int nsteps, int n_in, int rows, bool skew, std::vector<MscStep>& st, int& n_windows, int& why)
 {
-    static const int map16[16] = {0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15};
     const int PITCH = MSC_ROW_PITCH, SLOT = rows * MSC_ROW_PITCH, ZERO = 2 * SLOT;
     constexpr int PADDING = 6;                        // the kernel requests descriptors one block of six steps ahead
     st.assign((size_t)nsteps + PADDING, MscStep{0, 0});
@@ -21,7 +21,7 @@ bool step_table(const std::vector<map_t>& m, int nsteps, int n_in, int rows, boo
             const int u = map_index(m[4 * q + j]);
             if (u < 0) { off[j] = (uint32_t)ZERO; continue; }
             const int w = u >> 4, col = u & 15;
-            off[j] = (uint32_t)((w & 1) * SLOT + (skew ? map16[col] : 0) * PITCH + col);
+            off[j] = (uint32_t)((w & 1) * SLOT + (skew ? layout::tdi_row(col) : 0) * PITCH + col);
             if (wlo[q] < 0) wlo[q] = w;
             whi[q] = w;
         }
@@ -146,10 +146,7 @@ int fused_plan(dabphy_handle* h, uint32_t F, bool want_fic)
     }
     bool fic_in = false;
     if (want_fic && h->fused_fic && (use_sp || (h->fic_windows[v] > 0 && reach_ok((16 + (int)F - 1) / (int)F + 1)))) {
-        FusedClass fc{};
-        fc.steps = h->fic_steps[v].as<MscStep>(); fc.pairs = nullptr; fc.map = h->d_fic_map; fc.out = h->s_fib.as<uint8_t>();
-        fc.nbits = 768; fc.nsteps = 774; fc.n_windows = h->fic_windows[v]; fc.n_cw = (int32_t)(B * F * 4);
-        fc.n_pairs = 1; fc.kind = 1; fc.dedisperse = 1;
+        const FusedClass fc = fic_fused_class(h, h->s_fib.as<uint8_t>(), (int)(B * F * 4), v);
         items.push_back({fc.nsteps, (int)cls.size(), (fc.n_cw + 63) / 64});
         cls.push_back(fc);
         max_steps = std::max(max_steps, (size_t)fc.nsteps);
@@ -265,6 +262,22 @@ int sp_single_prepare(dabphy_handle* h, const FusedClass& fc, FusedArgs& a, hipS
     a.dec = h->vdec.as<uint2>(); a.dec_slot_cells = cells; a.prbs_words = h->d_prbs_words;
     a.sp2_warm = (int)h->sp2_tb_warm; a.sp2_resident = (int)h->sp2_tb_resident;
     return DABPHY_OK;
+}
+// The FIC of one class (the replay's one frame at a time, the dabphy_fic_decode seam): state-parallel when sp_single_ok says so -- the
+// class goes up once, here -- or through k_fic_gather + k_viterbi.  g names the soft bits and the class; launches take the frame selector.
+int fic_one_prepare(dabphy_handle* h, FicOneClass& o, const FicGatherArgs& g, hipStream_t st)
+{
+    o.g = g; o.v = vit_args(h, g.c); o.spa = FusedArgs{}; o.sp = sp_single_ok(h, (uint64_t)g.c.n_cw, g.c.nsteps);
+    if (!o.sp) return DABPHY_OK;
+    o.spa.soft = g.soft; o.spa.ens_stride = g.soft_ens_stride ? g.soft_ens_stride : (size_t)g.soft_ring * g.frame_stride; o.spa.soft_ring = g.soft_ring;
+    o.spa.n_ens = g.n_ens; o.spa.n_frames = g.n_frames; o.spa.desc = g.desc; o.spa.fic_frame_stride = g.frame_stride;
+    return sp_single_prepare(h, fic_fused_class(h, g.c.out, g.c.n_cw, -1), o.spa, st);
+}
+void fic_one_launch(const dabphy_handle* h, FicOneClass& o, int frame_sel, hipStream_t st)
+{
+    o.spa.fic_frame_sel = o.g.frame_sel = frame_sel;
+    if (o.sp) launch_sp(o.spa, h->sp1_two, sp_variant_for(o.g.c.nsteps), st);
+    else { launch_fic_gather(o.g, st); launch_viterbi(o.v, st); }
 }
 // Two code words per wavefront (k_viterbi_sp2: half the vector instructions per code word) pays once the code words outnumber the SIMDs
 // a few times over; below that the launch runs at the latency of ONE wave, and a wave that gathers and walks back two code words takes

@@ -8,6 +8,7 @@
 //   dabphy_mp2.hip          classic DAB (MP2) services: audio kinds, the MP2 frame check and its unit entry
 //   dabphy_getters.hip      everything a caller reads back after a batch, profiling, TII
 //   dabphy_au.hip           the bulk access-unit drain: the pack pass behind the filter (k_au.hip), its tables and its copy to the host
+//   soft_layout.h           where a code word's soft bits lie in the soft-bit ring, for kernels and host alike (dabphy_fused.hip's step tables)
 // Ownership: a device buffer (DevBuf) owns itself and is freed by its destructor; streams, events and page-locked blocks are created
 // through new_stream / new_event / pinned_alloc below and nowhere else, which register them with the handle for dabphy_destroy.
 #pragma once
@@ -416,6 +417,19 @@ inline int prepare_class(dabphy_handle* h, VitClass& c, int nbits, int n_cw, int
     c.sym = h->vsym.as<uint32_t>(); c.dec = h->vdec.as<uint2>(); c.out = h->vout.as<uint8_t>();
     return 0;
 }
+// ---- argument blocks that several translation units build, each stated once
+inline VitArgs vit_args(const dabphy_handle* h, const VitClass& c) { VitArgs v{}; v.c = c; v.prbs_words = h->d_prbs_words; return v; }
+// The FIC as a class of a fused or state-parallel launch: n_cw code words decoded into `out`; variant = the row-count build whose step
+// table it takes, below 0: none (the one-class launches gather by the map)
+inline FusedClass fic_fused_class(const dabphy_handle* h, uint8_t* out, int n_cw, int variant)
+{
+    FusedClass fc{}; fc.map = h->d_fic_map; fc.out = out; fc.nbits = 768; fc.nsteps = 774; fc.n_cw = n_cw; fc.n_pairs = 1; fc.kind = 1; fc.dedisperse = 1;
+    if (variant >= 0) { fc.steps = h->fic_steps[variant].as<MscStep>(); fc.n_windows = h->fic_windows[variant]; }
+    return fc;
+}
+// the FIC of ONE class, state-parallel or through k_fic_gather + k_viterbi (dabphy_fused.hip: fic_one_prepare / fic_one_launch): what
+// sp_single_ok decided, and the prepared arguments of either path
+struct FicOneClass { bool sp = false; FusedArgs spa{}; FicGatherArgs g{}; VitArgs v{}; };
 
 } // namespace dabphy
 
@@ -440,6 +454,8 @@ DABPHY_INTERNAL bool sp_single_ok(const dabphy_handle* h, uint64_t n_cw, int nst
 DABPHY_INTERNAL int sp_single_reserve(dabphy_handle* h, uint64_t n_cw, int nsteps);
 DABPHY_INTERNAL int sp_single_prepare(dabphy_handle* h, const FusedClass& fc, FusedArgs& a, hipStream_t st);
 DABPHY_INTERNAL int sp_variant_for(int nsteps);
+DABPHY_INTERNAL int fic_one_prepare(dabphy_handle* h, FicOneClass& o, const FicGatherArgs& g, hipStream_t st);     // called once: the class's staging copies go out here
+DABPHY_INTERNAL void fic_one_launch(const dabphy_handle* h, FicOneClass& o, int frame_sel, hipStream_t st);        // frame_sel as FicGatherArgs has it
 // the state-parallel launch of `a`: two code words per wavefront (k_viterbi_sp2) or one (k_viterbi_sp), as sp_two_for decided when the
 // decision scratch was laid out
 DABPHY_INTERNAL bool sp_two_for(const dabphy_handle* h, uint64_t n_cw);

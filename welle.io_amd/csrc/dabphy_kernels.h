@@ -134,13 +134,12 @@ struct FicGatherArgs {
     const FrameDesc* desc; int n_ens, n_frames;
     const map_t* map;       // [3096] mother-code index -> index into the 2304 punctured bits, MAP_ERASED = erasure
     VitClass c;
-    int frame_sel;          // 0: every frame of the batch, codeword (b F + f) 4 + q; f + 1: frame f only, codeword 4 b + q (c.n_cw = 4 B)
+    int frame_sel;          // 0: every frame of the batch; f + 1: frame f only (c.n_cw = 4 B).  Code word orders: soft_layout.h
 };
 
 // One (ensemble, sub-channel) PAIR of an MSC protection class.  Every ensemble of a batch selects its own sub-channels
 // (MscHandler::addSubchannel, msc-handler.cpp:61-103, is per receiver): a class is the list of the pairs of the whole batch that share
-// one protection profile, ordered by ensemble, then by position in that ensemble's list.  Code word of a class: cw = pair * R + r
-// (CIF r of this batch, R = 4 * n_frames).
+// one protection profile, ordered by ensemble, then by position in that ensemble's list (code word order of a class: soft_layout.h).
 struct MscPair {
     int32_t ens;            // ensemble of the batch
     int32_t start_bit;      // Subchannel::startAddr * 64: first soft bit of the sub-channel inside a CIF
@@ -182,11 +181,10 @@ constexpr int FUSED_VARIANTS = 3;
 constexpr int FUSED_ROWS[FUSED_VARIANTS] = {96, 144, 324};      // >= 64 + 15 * segments: 2 segments (>= 64 CIFs per batch), 5 (>= 16), 17 (>= 4)
 constexpr int FUSED_MIN_CIFS[FUSED_VARIANTS] = {64, 16, 4};
 constexpr uint32_t MSC_FIRST_USE = 1u << 15, MSC_LOAD_NEXT = 1u << 31, MSC_OFF_MASK = 0x7fffu;
-// One class of a fused launch (read through the constant address space).  kind 0 = an MSC protection class: code word
-// cw = pair * R + r ((ensemble, sub-channel) pair of the class's table, CIF r of this batch, R = 4 * n_frames); kind 1 = the FIC:
-// code word (b * n_frames + f) * 4 + q -- or, k_viterbi_sp only, 4 b + q of frame FusedArgs::fic_frame_sel - 1 alone (the replay of exact
-// batch mode); kind 2 (k_viterbi_sp only) = code words that lie one after the other in a plain array (the Viterbi::deconvolve /
-// Protection::deconvolve seams): FusedArgs::lin_in + cw * lin_stride, depunctured through `map` when there is one.
+// One class of a fused launch (read through the constant address space).  kind 0 = an MSC protection class; kind 1 = the FIC -- the
+// state-parallel kernels also take one frame of it alone, FusedArgs::fic_frame_sel (the replay of exact batch mode); code word orders of
+// both: soft_layout.h.  kind 2 (state-parallel kernels only) = code words that lie one after the other in a plain array (the
+// Viterbi::deconvolve / Protection::deconvolve seams): FusedArgs::lin_in + cw * lin_stride, depunctured through `map` when there is one.
 struct FusedClass {
     const MscStep* steps;     // [nsteps + 6] for the launch's row-count variant
     const MscPair* pairs;     // MSC: [n_pairs] (ensemble, start bit) of every pair, ensembles ascending

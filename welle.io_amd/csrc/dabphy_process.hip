@@ -164,18 +164,11 @@ static int replay_fic_frames(dabphy_handle* h, const Batch& b)
     // the FIC of ONE frame per step: a class of 4 B code words (frame_sel), decoded into the head of the FIB buffer -- the
     // full-batch FIC pass of decode_batch writes every FIB again
     const VitClass c = fic_class(h, (int)(B * 4));
-    FicGatherArgs g = fic_gather_args(h, b, c);
-    VitArgs v{}; v.c = c; v.prbs_words = h->d_prbs_words;
     CrcArgs k = crc_args(h, b);
-    // ... state-parallel when the batch of 4 B code words is small enough (one wavefront per code word: a replayed frame then costs a
-    // twentieth of a 774-step lane-per-code-word launch); the class is the same for every frame, only the frame selector moves
-    const bool fic_sp = sp_single_ok(h, (uint64_t)B * 4, c.nsteps);
-    FusedArgs spa{};
-    if (fic_sp) {
-        FusedClass fc{}; fc.map = h->d_fic_map; fc.out = c.out; fc.nsteps = c.nsteps; fc.nbits = 768; fc.n_cw = c.n_cw; fc.n_pairs = 1; fc.kind = 1; fc.dedisperse = 1;
-        spa.soft = b.da.soft; spa.ens_stride = b.ens_stride; spa.soft_ring = b.ring_frames; spa.n_ens = (int)B; spa.n_frames = (int)F; spa.desc = b.d_desc;
-        if ((r = sp_single_prepare(h, fc, spa, h->stream))) return r;
-    }
+    // (state-parallel when 4 B code words are few: a replayed frame then costs a twentieth of a 774-step lane-per-code-word launch;
+    // the class is the same for every frame, only the frame selector moves)
+    FicOneClass fic;
+    if ((r = fic_one_prepare(h, fic, fic_gather_args(h, b, c), h->stream))) return r;
     for (uint32_t f = 0; f < F; f++) {
         sa.frame = (int)f;
         launch_sync_find(sa, h->stream);
@@ -183,9 +176,8 @@ static int replay_fic_frames(dabphy_handle* h, const Batch& b)
         DemodArgs d1 = b.da; d1.frame_first = (int)f; d1.frame_count = 1; d1.con = nullptr; d1.osc_stats = nullptr;
         d1.chunk_count = (3 + b.da.chunk_len - 1) / b.da.chunk_len;          // the chunks that hold the FIC symbols 1..3 (demod_chunk may be 1 or 2)
         launch_demod(d1, (int)B, h->stream);
-        g.frame_sel = (int)f + 1; k.frame_sel = (int)f + 1;
-        if (fic_sp) { spa.fic_frame_sel = (int)f + 1; launch_sp(spa, h->sp1_two, sp_variant_for(c.nsteps), h->stream); }
-        else { launch_fic_gather(g, h->stream); launch_viterbi(v, h->stream); }
+        k.frame_sel = (int)f + 1;
+        fic_one_launch(h, fic, (int)f + 1, h->stream);
         launch_fib_crc(k, h->stream);
         CrcArgs kf = k; kf.frame_sel = 0; kf.frame_first = (int)f; kf.frame_count = 1;
         launch_fic_ratio(kf, h->stream);
@@ -231,8 +223,7 @@ static int queue_aux_work(dabphy_handle* h, const Batch& b)
     if (!h->fplan.fic_in) {
         mark(h, dabphy_handle::ST_FIC, false, fs);
         launch_fic_gather(fic_gather_args(h, b, b.fic), fs);
-        VitArgs v{}; v.c = b.fic; v.prbs_words = h->d_prbs_words;
-        launch_viterbi(v, fs);
+        launch_viterbi(vit_args(h, b.fic), fs);
     }
     h->tii_ran = false;
     if (h->tii_on) {
@@ -300,8 +291,7 @@ static int decode_unfused_classes(dabphy_handle* h, const Batch& b)
         g.map = cls.map.as<map_t>(); g.pairs = cls.pair_tab.as<MscPair>(); g.tiles = cls.tiles.as<int32_t>(); g.n_pairs = P; g.desc = b.d_desc; g.c = c;
         if (first_two) mark(h, dabphy_handle::ST_MSC_GATHER, false);
         launch_msc_gather(g, h->stream);
-        VitArgs v{}; v.c = c; v.prbs_words = h->d_prbs_words;
-        launch_viterbi(v, h->stream);
+        launch_viterbi(vit_args(h, c), h->stream);
         first_two = false;
     }
     if (!first_two) mark(h, dabphy_handle::ST_MSC_GATHER, true);       // (gather + decode pairs of all such classes)

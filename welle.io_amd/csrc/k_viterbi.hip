@@ -9,6 +9,9 @@
 //   DecoderAdapter::addtoFrame bit packing            decoder_adapter.cpp:55-67
 //   check_CRC_bits                                    various/MathHelper.h:53-80
 //
+// Where the soft bits of a code word lie in the soft-bit ring (CIF rows, the de-interleaver's row table, the FIC's quarters) and the
+// code word orders: soft_layout.h -- every gather below takes its addresses from there.
+//
 // MI355X mapping.  The reference decodes one codeword at a time with 64 scalar states.  Here ONE LANE
 // decodes ONE CODEWORD: a wavefront carries 64 independent codewords, the 64 path metrics of each live in
 // 32 VGPRs as pairs of uint16 and a trellis step is 32 x (2 plain 32-bit additions, v_pk_min_u16, v_pk_sub_i16) in a
@@ -21,6 +24,7 @@
 #include <cstdlib>
 #include <dabphy_wave_ops.h>
 #include "viterbi_acs.h"
+#include "soft_layout.h"
 
 namespace dabphy {
 
@@ -140,12 +144,11 @@ __global__ void __launch_bounds__(256) k_fic_gather(FicGatherArgs A)
     const int cw = g * 64 + lane;
     const int nsteps = A.c.nsteps;
     const bool live = cw < A.c.n_cw;
-    const int q = cw & 3;
-    const int bf = A.frame_sel ? (cw >> 2) * A.n_frames + (A.frame_sel - 1) : cw >> 2;     // bf = b * n_frames + f
+    const int bf = layout::fic_frame_of(cw, A.n_frames, A.frame_sel);                      // bf = b * n_frames + f
     const int b = live ? bf / A.n_frames : 0;
     const FrameDesc d = A.desc[live ? bf : 0];
     const size_t ens_stride = A.soft_ens_stride ? A.soft_ens_stride : (size_t)A.soft_ring * A.frame_stride;
-    const int8_t* __restrict__ src = A.soft + (size_t)b * ens_stride + (size_t)(d.frame_no % A.soft_ring) * A.frame_stride + 2304 * q;
+    const int8_t* __restrict__ src = A.soft + (size_t)b * ens_stride + layout::fic_cw_bytes(d.frame_no, A.soft_ring, A.frame_stride, cw);
     uint32_t* __restrict__ dst = A.c.sym + (size_t)g * nsteps * 64 + lane;
     for (int s = blockIdx.y * 4 + wave; s < nsteps; s += gridDim.y * 4) {
         uint32_t word = 0;
@@ -161,11 +164,8 @@ __global__ void __launch_bounds__(256) k_fic_gather(FicGatherArgs A)
 }
 
 // ------------------------------------------------------------------------------------------ MSC gather
-// Codeword order of an MSC class: cw = pair * R + r  ((ensemble, sub-channel) pair of the class's table -- every ensemble
-// selects its own sub-channels, msc-handler.cpp:61-103 --, CIF r of this batch, R = 4 * n_frames), so the 64 lanes of a
-// Viterbi wave are consecutive CIFs of one sub-channel (at most a few pairs per group).  Soft bit u of the logical frame emitted at CIF c comes from CIF
-// c - 16 + map16[u & 15] (dab-audio.cpp:113,138-143: tempX[i] = hist[(idx + map[i & 15]) & 15][i], read BEFORE the
-// current CIF is stored): the time de-interleaver is an address computation on the soft-bit ring, never a copy.
+// Code word order of an MSC class and the time de-interleaver as an address computation on the soft-bit ring: soft_layout.h.  The 64
+// lanes of a Viterbi wave are consecutive CIFs of one sub-channel (at most a few pairs per group).
 //
 // Data movement: a work-group owns one group of 64 codewords and walks the trellis in tiles of GT_STEPS steps.
 // For a tile it stages the needed byte columns [u_lo, u_hi) of every source CIF row (<= 64 + 15 rows per (b, m)
@@ -195,7 +195,6 @@ __global__ void __launch_bounds__(256) k_msc_gather(MscGatherArgs A)
     const long long c_glob = 4 * A.desc[(size_t)b * A.n_frames].frame_no + r;   // CIF whose arrival emits this logical frame
     const size_t ens_stride = A.soft_ens_stride ? A.soft_ens_stride : (size_t)A.soft_ring * SOFT_PER_FRAME;
     const size_t ens_base = (size_t)b * ens_stride + (size_t)mine.start_bit;
-    const int map16[16] = {0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15};
     uint32_t* __restrict__ dst = A.c.sym + (size_t)g * nsteps * 64 + lane;
 
     if (wave == 0) { s_pair[lane] = pair; s_c[lane] = c_glob; }
@@ -215,7 +214,7 @@ __global__ void __launch_bounds__(256) k_msc_gather(MscGatherArgs A)
             for (int k = 0; k < need; k++) {
                 const long long c_src = s_c[l] - 16 + k;
                 long long src = -1;
-                if (c_src >= 0) src = pbase + ((long long)((c_src >> 2) % A.soft_ring) * 75 + 3 + 18 * (int)(c_src & 3)) * SOFT_PER_SYM;
+                if (c_src >= 0) src = pbase + (long long)layout::cif_row_bytes(c_src, A.soft_ring);
                 s_rowsrc[nrows + k] = src;
             }
             for (int k = l; k <= e; k++) s_rowbase[k] = nrows + (k - l);
@@ -237,8 +236,8 @@ __global__ void __launch_bounds__(256) k_msc_gather(MscGatherArgs A)
                 const int u = map_index(A.map[4 * s + j]);
                 int v = 0;
                 if (u >= 0 && live) {
-                    const long long c_src = c_glob - 16 + map16[u & 15];
-                    if (c_src >= 0) v = A.soft[ens_base + ((size_t)((c_src >> 2) % A.soft_ring) * 75 + 3 + 18 * (int)(c_src & 3)) * SOFT_PER_SYM + u];
+                    const long long c_src = c_glob - 16 + layout::tdi_row(u & 15);
+                    if (c_src >= 0) v = A.soft[ens_base + layout::cif_row_bytes(c_src, A.soft_ring) + u];
                 }
                 v += 127; v = v < 0 ? 0 : v; v = v > 255 ? 255 : v;
                 word |= (uint32_t)v << (8 * j);
@@ -256,7 +255,7 @@ __global__ void __launch_bounds__(256) k_msc_gather(MscGatherArgs A)
         // map entry -> byte offset inside a tile row plus the row shift of the time de-interleaver; -1 = erasure
         if (t < 4 * (s1 - s0)) {
             const int u = map_index(A.map[4 * s0 + t]);
-            s_map[t] = (u >= 0) ? (map16[u & 15] * (GT_PITCHW * 4) + (u - u_lo)) : -1;
+            s_map[t] = (u >= 0) ? (layout::tdi_row(u & 15) * (GT_PITCHW * 4) + (u - u_lo)) : -1;
         }
         // rows travel HBM -> LDS by LDS-DMA: nothing waits between the (up to 28) row requests of a wave
         for (int row = wave; row < nrows; row += 4) {
@@ -299,8 +298,8 @@ __global__ void __launch_bounds__(256) k_msc_gather(MscGatherArgs A)
 //
 // A wave (64 code words) keeps in LDS a sliding WINDOW of the soft-bit rows it decodes from:
 //   rows    MSC class: the source CIFs of its code words.  Code words are consecutive CIFs of consecutive (ensemble, sub-channel)
-//           pairs; byte u of the frame emitted at CIF c comes from CIF c - 16 + map16[u & 15] (time de-interleaver,
-//           dab-audio.cpp:113,138-143), so a run of n lanes of one pair (a segment) needs n + 15 rows: 64 + 15 * segments in all.
+//           pairs; byte u of the frame emitted at CIF c comes from one of the 16 CIFs before it (time de-interleaver, soft_layout.h),
+//           so a run of n lanes of one pair (a segment) needs n + 15 rows: 64 + 15 * segments in all.
 //           Batches of >= 64 CIFs per sub-channel give <= 2 segments (96 rows), >= 16 CIFs <= 5 (144 rows), >= 4 CIFs <= 17 (324
 //           rows): three builds of the kernel.  FIC: one row per code word (its 2304 punctured bits, fic-handler.cpp:158-191), no skew.
 //   columns 16-byte windows of the punctured bit stream: window w = bytes [16 w, 16 w + 16).  Two windows are resident (slot w & 1),
@@ -466,25 +465,23 @@ __global__ void __launch_bounds__(64, OCC) k_viterbi_fused(FusedArgs A)
                     const int pb = pp.ens;
                     const long long c_src = 4 * A.desc[(size_t)pb * F].frame_no + (j == 0 ? r0 : 0) - 16 + idx;
                     if (c_src >= 0)
-                        src = (uint32_t)(((size_t)(pb - pb0) * A.ens_stride + (size_t)pp.start_bit +
-                                          ((size_t)((c_src >> 2) % A.soft_ring) * 75 + 3 + 18 * (int)(c_src & 3)) * SOFT_PER_SYM) >> 4);     // (start_bit is a multiple of 64)
+                        src = (uint32_t)(((size_t)(pb - pb0) * A.ens_stride + (size_t)pp.start_bit + layout::cif_row_bytes(c_src, A.soft_ring)) >> 4);     // (start_bit is a multiple of 64)
                 }
             }
             rowptr[row] = src;
         }
     } else {
         // FIC: code word -> (ensemble, frame slot, quarter); one row per code word: the 2304 soft bits of that quarter of symbols 1..3
-        auto bf_of = [&](int c) { return c >> 2; };
         nrows = 64; rb = lane;
-        pb0 = bf_of((int)cw0) / F;
+        pb0 = layout::fic_frame_of((int)cw0, F, 0) / F;
         for (int row = lane; row < ROWS; row += 64) {
             uint32_t src = zero16;
             const int cwr = (int)cw0 + row;
             if (row < 64 && cwr < n_cw) {
-                const int bf = bf_of(cwr), b = bf / F;
+                const int bf = layout::fic_frame_of(cwr, F, 0), b = bf / F;
                 const FrameDesc& d = A.desc[bf];
                 if (d.valid == 1)
-                    src = (uint32_t)(((size_t)(b - pb0) * A.ens_stride + (size_t)(d.frame_no % A.soft_ring) * SOFT_PER_FRAME + (size_t)2304 * (cwr & 3)) >> 4);
+                    src = (uint32_t)(((size_t)(b - pb0) * A.ens_stride + layout::fic_cw_bytes(d.frame_no, A.soft_ring, SOFT_PER_FRAME, cwr)) >> 4);
             }
             rowptr[row] = src;
         }

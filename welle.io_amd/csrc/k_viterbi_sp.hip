@@ -30,7 +30,8 @@
 // index).  Histories come back 30 steps per load, one word per lane; a step reads the word of lane l with v_readlane.
 //
 // Gather.  The soft bits of a code word are fetched once, up front, by all 64 lanes (lane j: steps j, j + 64, ...) straight from the
-// soft-bit ring -- time de-interleaver as an address computation, depuncturing by the class's map -- and parked in LDS as one packed
+// soft-bit ring -- time de-interleaver as an address computation (soft_layout.h states the ring's layout and the code word orders,
+// viterbi_gather.h is the gather), depuncturing by the class's map -- and parked in LDS as one packed
 // word per step (the three branch-metric inputs, doubled and biased: x0 = v0 + v3 because outputs 0 and 3 share a generator).
 //
 // Who launches it (dabphy_fused.hip).  A batch of at most 16 384 code words: every MSC class and the FIC of the batch, kinds 0 and 1 of
@@ -41,13 +42,13 @@
 #include "dabphy_kernels.h"
 #include <dabphy_wave_ops.h>
 #include "viterbi_acs.h"
+#include "viterbi_gather.h"
 
 namespace dabphy {
 
 constexpr int SP_HIST = 30;                       // trellis steps per decision history word (k_viterbi_sp)
 namespace sp {
 __device__ __forceinline__ int rotl6(int x, int r) { r %= 6; return r == 0 ? x : (((x << r) | (x >> (6 - r))) & 63); }
-__device__ __forceinline__ int brev4(int i) { return ((i & 1) << 3) | ((i & 2) << 1) | ((i & 4) >> 1) | ((i & 8) >> 3); }   // = map16[i] of dab-audio.cpp:113
 }
 
 template <int MAXSTEPS, int OCC>
@@ -56,50 +57,20 @@ __global__ void __launch_bounds__(64, OCC) k_viterbi_sp(FusedArgs A)
     __shared__ uint32_t sym[MAXSTEPS + 2 * SP_HIST];
     __shared__ long long s_rowoff[16];
     const int lane = threadIdx.x;
-    const int F = A.n_frames, R = 4 * F;
     const uint32_t wk = as_constant(A.work)[blockIdx.x >> 6];
     const DABPHY_CONST_AS FusedClass& C = as_constant(A.cls)[wk >> 24];
     const int cw = (int)(wk & 0xffffffu) * 64 + (int)(blockIdx.x & 63u);
     const int nsteps = C.nsteps, nbits = C.nbits;
     if (cw >= C.n_cw || nsteps > MAXSTEPS) return;
 
-    // ---- where this code word's soft bits lie: 16 row offsets (one per column u & 15 of the time de-interleaver), -1 = no such CIF
-    const int8_t* base;
-    if (C.kind == 0) {
-        const int pair = cw / R, r = cw - pair * R;
-        const MscPair pp = C.pairs[pair];                                   // every ensemble selects its own sub-channels (msc-handler.cpp:61-103)
-        const int b = pp.ens;
-        base = A.soft + (size_t)b * A.ens_stride + (size_t)pp.start_bit;
-        if (lane < 16) {
-            const long long c_src = 4 * A.desc[(size_t)b * F].frame_no + r - 16 + sp::brev4(lane);      // dab-audio.cpp:113,138-143
-            s_rowoff[lane] = c_src >= 0 ? ((long long)((c_src >> 2) % A.soft_ring) * 75 + 3 + 18 * (int)(c_src & 3)) * SOFT_PER_SYM : -1;
-        }
-    } else if (C.kind == 1) {
-        const int fsel = A.fic_frame_sel;
-        const int bf = fsel ? (cw >> 2) * F + (fsel - 1) : cw >> 2, b = bf / F;
-        const FrameDesc& d = A.desc[bf];
-        const size_t fstride = A.fic_frame_stride ? A.fic_frame_stride : (size_t)SOFT_PER_FRAME;
-        base = A.soft + (size_t)b * A.ens_stride + (size_t)(d.frame_no % A.soft_ring) * fstride + (size_t)2304 * (cw & 3);
-        if (lane < 16) s_rowoff[lane] = d.valid == 1 ? 0 : -1;
-    } else {
-        base = A.lin_in + (size_t)cw * A.lin_stride;                     // a code word of the linear seams: no de-interleaver
-        if (lane < 16) s_rowoff[lane] = 0;
-    }
+    // ---- where this code word's soft bits lie (viterbi_gather.h), then one packed word per step
+    const int8_t* const base = locate(A, C, cw, lane, s_rowoff);
     __syncthreads();
     {
         const map_t* __restrict__ map = C.map;
         for (int s = lane; s < nsteps; s += 64) {
-            uint2 mm = make_uint2(0, 0);
-            if (map) mm = *reinterpret_cast<const uint2*>(map + 4 * s);                    // four map entries
             int v[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int u = map ? map_index(((j < 2 ? mm.x : mm.y) >> (16 * (j & 1))) & 0xffffu) : 4 * s + j;
-                long long off = -1;
-                if (u >= 0) off = s_rowoff[u & 15];
-                v[j] = off >= 0 ? (int)base[off + u] : 0;
-                if (v[j] < -127) v[j] = -127;                               // -128 maps to symbol 0 like -127 (viterbi.cpp:233-236): the demapper never produces it, a seam's caller may
-            }
+            fetch_step(map, s, base, s_rowoff, v);
             // the three branch-metric inputs of the step, doubled and biased as the trellis takes them (viterbi.cpp:233-238 puts the symbol
             // levels at v + 127: bm(p) = 510 + e0 (x0 - 1) + e1 (v1 - 1/2) + e2 (v2 - 1/2), x0 = v0 + v3): 12 + 10 + 10 signed bits
             sym[s] = ((uint32_t)(2 * (v[0] + v[3]) - 2) & 0xfffu) | (((uint32_t)(2 * v[1] - 1) & 0x3ffu) << 12) | ((uint32_t)(2 * v[2] - 1) << 22);

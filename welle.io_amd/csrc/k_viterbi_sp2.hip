@@ -4,6 +4,7 @@
 // (viterbi.cpp:227-339), the depuncturing of EEPProtection / UEPProtection::deconvolve (eep-protection.cpp:115-152,
 // uep-protection.cpp:169-239) and FicHandler::processFicInput (fic-handler.cpp:144-204), DabAudio's time de-interleaver
 // (dab-audio.cpp:113-149), energy dispersal and bit packing -- for the batches the lane-per-code-word kernel is the wrong shape for,
+// (where a code word's soft bits lie: soft_layout.h; the gather both state-parallel kernels share: viterbi_gather.h),
 // at half the instructions per code word of round 4's k_viterbi_sp (which stays for the smallest batches and as
 // dabphy_config.decode_shape = 3).  Code words of any length: the LDS table of branch-metric sums holds 480 trellis steps at a time.
 //
@@ -41,13 +42,13 @@
 #include "dabphy_kernels.h"
 #include <dabphy_wave_ops.h>
 #include "viterbi_acs.h"
+#include "viterbi_gather.h"
 
 namespace dabphy {
 
 constexpr int SP2_HIST = 30;                      // trellis steps per decision history word: a multiple of the five layouts and of the six-step code word granule
 namespace sp2 {
 __device__ __forceinline__ int rotl5(int x, int r) { r %= 5; return r == 0 ? x : (((x << r) | (x >> (5 - r))) & 31); }
-__device__ __forceinline__ int brev4(int i) { return ((i & 1) << 3) | ((i & 2) << 1) | ((i & 4) >> 1) | ((i & 8) >> 3); }   // = map16[i] of dab-audio.cpp:113
 __host__ __device__ constexpr int xbit(int f) { return 4 - f; }                  // lane bit of the exchange after a step in layout f
 __host__ __device__ constexpr int inbit(int f) { return f == 0 ? 0 : f == 1 ? -1 : 5 - f; }   // lane bit that tells whether a lane's inputs are swapped in layout f (-1: never)
 }
@@ -62,7 +63,6 @@ __global__ void __launch_bounds__(64, OCC) k_viterbi_sp2(FusedArgs A)
     __shared__ __attribute__((aligned(8))) int16_t tab[2][CHUNK * 4 + 4];                   // per code word and step: +a0+a1+a2, -a0+a1+a2, +a0-a1+a2, -a0-a1+a2 (+ 8 bytes: the halves' reads fall on different banks)
     __shared__ long long s_rowoff[2][16];
     const int lane = threadIdx.x, half = lane >> 5, j = lane & 31;
-    const int F = A.n_frames, R = 4 * F;
     const uint32_t wk = as_constant(A.work)[blockIdx.x >> 5];
     const DABPHY_CONST_AS FusedClass& C = as_constant(A.cls)[wk >> 24];
     const int cw_a = (int)(wk & 0xffffffu) * 64 + 2 * (int)(blockIdx.x & 31u);
@@ -71,44 +71,15 @@ __global__ void __launch_bounds__(64, OCC) k_viterbi_sp2(FusedArgs A)
     const bool second = cw_a + 1 < C.n_cw;                                  // (an odd class: the last wave's upper half decodes the same code word again, its output is dropped)
     const int cw = cw_a + (second ? half : 0);
 
-    // ---- where this half's code word lies: 16 row offsets (one per column u & 15 of the time de-interleaver), -1 = no such CIF
-    const int8_t* base;
-    if (C.kind == 0) {
-        const int pair = cw / R, r = cw - pair * R;
-        const MscPair pp = C.pairs[pair];                                   // every ensemble selects its own sub-channels (msc-handler.cpp:61-103)
-        const int b = pp.ens;
-        base = A.soft + (size_t)b * A.ens_stride + (size_t)pp.start_bit;
-        if (j < 16) {
-            const long long c_src = 4 * A.desc[(size_t)b * F].frame_no + r - 16 + sp2::brev4(j);      // dab-audio.cpp:113,138-143
-            s_rowoff[half][j] = c_src >= 0 ? ((long long)((c_src >> 2) % A.soft_ring) * 75 + 3 + 18 * (int)(c_src & 3)) * SOFT_PER_SYM : -1;
-        }
-    } else if (C.kind == 1) {
-        const int fsel = A.fic_frame_sel;
-        const int bf = fsel ? (cw >> 2) * F + (fsel - 1) : cw >> 2, b = bf / F;
-        const FrameDesc& d = A.desc[bf];
-        const size_t fstride = A.fic_frame_stride ? A.fic_frame_stride : (size_t)SOFT_PER_FRAME;
-        base = A.soft + (size_t)b * A.ens_stride + (size_t)(d.frame_no % A.soft_ring) * fstride + (size_t)2304 * (cw & 3);
-        if (j < 16) s_rowoff[half][j] = d.valid == 1 ? 0 : -1;
-    } else {
-        base = A.lin_in + (size_t)cw * A.lin_stride;                        // a code word of the linear seams: no de-interleaver
-        if (j < 16) s_rowoff[half][j] = 0;
-    }
+    // ---- where this half's code word lies (viterbi_gather.h)
+    const int8_t* const base = locate(A, C, cw, j, s_rowoff[half]);
     __syncthreads();
     // the table of steps [c0, c0 + n): entry (s - c0)
     auto fill = [&](int c0, int n) {
         const map_t* __restrict__ map = C.map;
         for (int s = c0 + j; s < c0 + n; s += 32) {
-            uint2 mm = make_uint2(0, 0);
-            if (map) mm = *reinterpret_cast<const uint2*>(map + 4 * s);                    // four map entries
             int v[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int u = map ? map_index(((q < 2 ? mm.x : mm.y) >> (16 * (q & 1))) & 0xffffu) : 4 * s + q;
-                long long off = -1;
-                if (u >= 0) off = s_rowoff[half][u & 15];
-                v[q] = off >= 0 ? (int)base[off + u] : 0;
-                if (v[q] < -127) v[q] = -127;                               // -128 maps to symbol 0 like -127 (viterbi.cpp:233-236)
-            }
+            fetch_step(map, s, base, s_rowoff[half], v);
             // the three branch-metric inputs, doubled and biased as the trellis takes them (viterbi.cpp:233-238 puts the symbol levels at
             // v + 127: bm(p) = 510 + e0 (x0 - 1) + e1 (v1 - 1/2) + e2 (v2 - 1/2), x0 = v0 + v3), and their four sign combinations
             const int a0 = 2 * (v[0] + v[3]) - 2, a1 = 2 * v[1] - 1, a2 = 2 * v[2] - 1;
