@@ -714,7 +714,7 @@ def check_fine_corrector_on_the_edge(d_factory):
 
 
 def check_relock_after_long_lock(d_factory, n_locked=70, F=1):       # one frame per call: the coarse corrector sees the FIC ratio as the reference does
-    """lock held for more than the 64 window searches the synchroniser remembers, then a dropout: k_acquire cannot replay sLevel
+    """lock held for more than the 64 window searches the synchroniser remembers, then a dropout: k_sync_find's acquisition head (acquire_body) cannot replay sLevel
     from the last acquisition and brackets it instead (runs from 0 and from 3e38 over the remembered 64 frames); the two runs must
     have met, and the re-acquisition must land where the reference's does"""
     T_F = 196608

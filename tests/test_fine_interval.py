@@ -1,13 +1,17 @@
-"""The arithmetic behind k_sync_finish's fast path (welle.io_amd/csrc/k_sync.hip: fine_decided), restated in numpy and checked
+"""The arithmetic behind k_sync_finish's fast path (welle.io_amd/csrc/sync_fine.h: fine_decided), restated in numpy and checked
 against brute force: (1) the error bound of the reference's ordered float32 summation derived from block sums really bounds it,
-(2) whenever the interval test calls the int16 fine-corrector step "decided", it is the step the ordered sums give.
+(2) whenever the interval test calls the int16 fine-corrector step "decided", it is the step the ordered sums give; and (3) the
+header itself, compiled for the host (tests/native/fine_check.cpp), on the same trials as (2).
 The kernel itself is covered by the parity suites (correctors frame by frame against the oracle, both paths taken)."""
 import ctypes
 import math
+import os
+import subprocess
 
 import numpy as np
 import pytest
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 75 * 504
 U = 2.0 ** -24
 ROWS_PER_BLOCK = 8
@@ -89,4 +93,36 @@ def test_decided_means_equal_to_ordered_sums():
         else:
             n_decided += 1
             assert got == want, (trial, target, got, want)
+    assert n_decided >= 30 and n_declined >= 3, (n_decided, n_declined)
+
+
+def test_header_fine_decided_on_the_same_trials(tmp_path):
+    """the real fine_decided (sync_fine.h, block sums formed as sync_finish_body forms them) on the 60 trials of
+    test_decided_means_equal_to_ordered_sums: never wrong when it decides, and it decides exactly where the restatement does"""
+    rng = np.random.RandomState(7)
+    want, restated = [], []
+    with open(tmp_path / "trials.f32", "wb") as f:
+        for trial in range(60):                                                   # (the same draws in the same order as above)
+            k = rng.randint(-3, 4)
+            target = k * math.pi / 50 + rng.choice([0.0, 1.0]) * rng.uniform(-2e-4, 2e-4) + rng.choice([0.0, 1.0]) * rng.uniform(-0.03, 0.03)
+            amp = 10.0 ** rng.uniform(-2.5, -0.5)
+            re = (amp * math.cos(target) * (1 + 0.2 * rng.randn(N)) + 0.3 * amp * rng.randn(N)).astype(np.float32)
+            im = (amp * math.sin(target) * (1 + 0.2 * rng.randn(N)) + 0.3 * amp * rng.randn(N)).astype(np.float32)
+            fine_old = int(rng.randint(-400, 400))
+            want.append(fine_from_arg(fine_old, libm.atan2f(seq_sum_f32(im), seq_sum_f32(re))))
+            restated.append(decided(fine_old, re, im))
+            np.float32(fine_old).tofile(f); re.tofile(f); im.tofile(f)
+    exe = str(tmp_path / "fine_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "tests", "hipemu"),
+                           "-I", os.path.join(ROOT, "welle.io_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "native", "fine_check.cpp")])
+    got = [tuple(int(x) for x in line.split()) for line in subprocess.check_output([exe, str(tmp_path / "trials.f32")]).decode().splitlines()]
+    assert len(got) == 60
+    n_decided = n_declined = 0
+    for trial, ((dec, value), w, r) in enumerate(zip(got, want, restated)):
+        assert bool(dec) == (r is not None), (trial, dec, value, r)
+        if dec:
+            n_decided += 1
+            assert value == w, (trial, value, w)
+        else:
+            n_declined += 1
     assert n_decided >= 30 and n_declined >= 3, (n_decided, n_declined)

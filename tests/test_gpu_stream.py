@@ -260,8 +260,8 @@ def test_low_snr_batches_with_coarse_corrector(gpu, snr, cfo, F, seed):
 
 
 def test_dropout_in_batch_mode(gpu):
-    """a dropout decoded four frames per call: the slot after the failed window search re-acquires at once (k_acquire is queued before
-    every frame step), MSC rows stay packed, the superframe filter walks the frames that exist"""
+    """a dropout decoded four frames per call: the slot after the failed window search re-acquires at once (k_sync_find's acquisition head,
+    acquire_body, runs in front of every frame step's window search), MSC rows stay packed, the superframe filter walks the frames that exist"""
     P.check_dropout_batch(factory)
 
 

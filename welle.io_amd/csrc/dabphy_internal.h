@@ -8,6 +8,8 @@
 //   dabphy_mp2.hip          classic DAB (MP2) services: audio kinds, the MP2 frame check and its unit entry
 //   dabphy_getters.hip      everything a caller reads back after a batch, profiling, TII
 //   dabphy_au.hip           the bulk access-unit drain: the pack pass behind the filter (k_au.hip), its tables and its copy to the host
+//   k_sync.hip              the synchroniser's kernels, with one header per reference function: sync_window.h (PhaseReference::findIndex:
+//                           impulse response, the three window-index methods), sync_fine.h (the fine corrector's step and its interval test; host-compilable); block_reduce.h (their work-group reduction)
 //   soft_layout.h           where a code word's soft bits lie in the soft-bit ring, for kernels and host alike (dabphy_fused.hip's step tables)
 // Ownership: a device buffer (DevBuf) owns itself and is freed by its destructor; streams, events and page-locked blocks are created
 // through new_stream / new_event / pinned_alloc below and nowhere else, which register them with the handle for dabphy_destroy.
@@ -200,7 +202,7 @@ struct dabphy_handle {
     hipEvent_t ev_beg[ST_COUNT]{}, ev_end[ST_COUNT]{};
     bool ev_used[ST_COUNT]{};
     DevBuf rs_first, rs_result, rs_rows;
-    DevBuf s_hist;                          // [B][HIST_CAP] window searches since the last acquisition (sLevel replay in k_acquire)
+    DevBuf s_hist;                          // [B][HIST_CAP] window searches since the last acquisition (sLevel replay in k_sync_find's acquisition head, acquire_body)
     // TII (RadioReceiverOptions::decodeTII): constants, per-batch scratch, per-ensemble sums that live across batches
     bool tii_on = false; bool tii_ran = false;
     bool track_slevel = false;        // dabphy_set_track_slevel: sLevel follows every tracked frame instead of catching up at a loss of lock

@@ -377,7 +377,6 @@ void dump_chain_ts();
 void launch_sync_find(const SyncArgs& a, hipStream_t s);
 void launch_sync_wide(const SyncArgs& a, hipStream_t s, hipEvent_t front = nullptr);      // front: recorded behind the wide pass proper (searches, sums, judge), in front of the find chain's rounds
 void launch_sync_finish(const SyncArgs& a, hipStream_t s);
-void launch_acquire(const SyncArgs& a, hipStream_t s);
 void launch_slevel_catchup(const SyncArgs& a, hipStream_t s);
 
 } // namespace dabphy

@@ -1,11 +1,12 @@
 // welle.io_amd/csrc/k_sync.hip -- time/frequency synchronisation of OFDMProcessor::run, one work-group per ensemble.
 //
 // Replaces (reference file:line, relative to src/backend):
-//   OFDMProcessor::run, notSynced .. SyncOnEndNull      ofdm-processor.cpp:249-319     -> k_acquire
-//   OFDMProcessor::run, SyncOnPhase .. ReadyForNewFrame ofdm-processor.cpp:324-490     -> k_sync_frame
+//   OFDMProcessor::run, notSynced .. SyncOnEndNull      ofdm-processor.cpp:249-319     -> acquire_body, the head of k_sync_find
+//   OFDMProcessor::run, SyncOnPhase .. ReadyForNewFrame ofdm-processor.cpp:324-490     -> k_sync_find, k_sync_finish
 //   OFDMProcessor::getSample(s) oscillator              ofdm-processor.cpp:145-224     (closed-form phase, table gather)
-//   PhaseReference::findIndex                           phasereference.cpp:73-256      (ThresholdBeforePeak, StrongestPeak)
-//   OFDMProcessor::processPRS (PatternOfZeros)          ofdm-processor.cpp:537-616
+//   PhaseReference::findIndex                           phasereference.cpp:73-256      -> sync_window.h
+//   OFDMProcessor::processPRS, getMiddle                ofdm-processor.cpp:537-644     (inline in sync_find_body, step 7)
+//   the fine corrector's step                           ofdm-processor.cpp:450-451     -> sync_fine.h
 //
 // The chain frame -> frame is inherently serial per ensemble (the window position and the fine corrector of
 // frame n+1 depend on frame n), so the batch dimension is the ensemble: B work-groups per launch, one launch
@@ -17,36 +18,11 @@
 #include <dabphy_wave_ops.h>
 #include "osc_exact.h"
 #include "mix2048.h"
+#include "block_reduce.h"
+#include "sync_fine.h"
+#include "sync_window.h"
 
 namespace dabphy {
-
-__device__ __forceinline__ float block_max(float x, float* red, int t)
-{
-    __syncthreads();
-    red[t] = x;
-    __syncthreads();
-    for (int s = FFT_THREADS / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] = fmaxf(red[t], red[t + s]);
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ int block_min_int(int x, int* red, int t)
-{
-    __syncthreads();
-    red[t] = x;
-    __syncthreads();
-    for (int s = FFT_THREADS / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] = red[t] < red[t + s] ? red[t] : red[t + s];
-        __syncthreads();
-    }
-    const int r = red[0];
-    __syncthreads();
-    return r;
-}
 
 // The frame chain, two launches per frame on the sync stream:
 //   k_sync_find(frame)      B work-groups: PRS window search (+ coarse corrector); leaves the descriptor "pending" (valid = 2)
@@ -58,7 +34,8 @@ __device__ __forceinline__ int block_min_int(int x, int* red, int t)
 // ofdm-processor.cpp:447-490: correctors, null symbol, state commit (one thread)
 // OFDMProcessor::sLevel is advanced by every sample getSample(s) hands out (ofdm-processor.cpp:174,216) but only ever read by the
 // null-symbol search after a loss of lock (:284,:303).  While tracking, the synchroniser therefore just records what was pulled
-// (one descriptor per window search); k_acquire replays those samples through the recurrence when it is next needed.
+// (one descriptor per window search); k_sync_find's acquisition head (acquire_body) replays those samples through the recurrence
+// when it is next needed.
 template <class State>
 __device__ __forceinline__ void hist_append(const SyncArgs& A, int b, State& st, const FrameDesc& d)
 {
@@ -69,60 +46,6 @@ __device__ __forceinline__ void hist_append(const SyncArgs& A, int b, State& st,
     }
     h[(st.hist_head + st.hist_count) % A.hist_cap] = d;
     st.hist_count++;
-}
-
-// ofdm-processor.cpp:450-451: fineCorrector (int16) += 0.1 * arg(FreqCorr) / M_PI * (carrierDiff / 2)
-__device__ __forceinline__ int32_t fine_from_arg(int32_t fine_old, float a)
-{
-    return (int32_t)(int16_t)((double)fine_old + 0.1 * (double)a / M_PI * (1000 / 2));
-}
-
-// next float towards +inf (up) or -inf
-__device__ __forceinline__ float f32_step(float x, bool up)
-{
-    union { float f; uint32_t u; } v; v.f = x;
-    if ((v.u & 0x7fffffffu) == 0) { v.u = up ? 1u : 0x80000001u; return v.f; }
-    const bool neg = (v.u >> 31) != 0;
-    v.u += (neg != up) ? 1u : 0xffffffffu;                  // away from zero when the step and the sign agree
-    return v.f;
-}
-__device__ __forceinline__ float f32_down(double x) { float f = (float)x; if ((double)f > x) f = f32_step(f, false); return f; }
-__device__ __forceinline__ float f32_up(double x) { float f = (float)x; if ((double)f < x) f = f32_step(f, true); return f; }
-
-// The only thing the reference takes from FreqCorr is the int16 it adds to the fine corrector.  The float sums it accumulates in
-// index order differ from the exact sums by at most E = u Q / (1 - (n + 1) u), Q >= sum over all prefixes |S_k|, u = 2^-24 (each
-// addition errs by at most u times its own result; Higham, "Accuracy and Stability of Numerical Algorithms", section 4.2, with the
-// computed prefixes bounded by the exact ones plus E).  Q comes from block sums: a prefix that ends inside block b is at most
-// |sum of the blocks before b| + sum of the magnitudes inside b.  atan2 is monotone along the edges of a box that avoids the
-// origin and the branch cut, atan2f is within 2 ulp of it, and the corrector expression is monotone in the angle.  So evaluating
-// it at the ends of the interval decides the int16 whenever both ends agree -- all but about one frame in 5000 -- and otherwise the
-// caller falls back to the ordered float sums.  blk[b][0..3] = sum re, sum im, sum |re|, sum |im| of block b (double precision, any
-// order), m[b] = products in block b.  Returns true when decided.
-constexpr int FIN_BLOCK_ROWS = 8, FIN_BLOCKS = (75 + FIN_BLOCK_ROWS - 1) / FIN_BLOCK_ROWS;
-__device__ __forceinline__ bool fine_decided(int32_t fine_old, const double (*blk)[4], int32_t& fine_new)
-{
-    constexpr double n = 75.0 * 504.0, u = 0x1p-24;
-    double sre = 0.0, sim = 0.0, are = 0.0, aim = 0.0, qre = 0.0, qim = 0.0;
-    for (int b = 0; b < FIN_BLOCKS; b++) {
-        const double m = 504.0 * ((b + 1) * FIN_BLOCK_ROWS <= 75 ? FIN_BLOCK_ROWS : 75 - b * FIN_BLOCK_ROWS);
-        qre += m * (fabs(sre) + blk[b][2]); qim += m * (fabs(sim) + blk[b][3]);
-        sre += blk[b][0]; sim += blk[b][1]; are += blk[b][2]; aim += blk[b][3];
-    }
-    constexpr double k = u / (1.0 - (n + 1.0) * u) * (1.0 + 0x1p-30);
-    constexpr double dsum = n * 0x1p-51;                              // this path's own (double precision) summation errors, generously
-    const double ere = k * qre * (1.0 + dsum) + dsum * are + 1e-30, eim = k * qim * (1.0 + dsum) + dsum * aim + 1e-30;
-    const double r_lo = sre - ere, r_hi = sre + ere, i_lo = sim - eim, i_hi = sim + eim;
-    if (!(r_lo > -1e30) || !(r_hi < 1e30) || !(i_lo > -1e30) || !(i_hi < 1e30)) return false;    // (also NaN)
-    const float xl = f32_down(r_lo), xh = f32_up(r_hi), yl = f32_down(i_lo), yh = f32_up(i_hi);
-    // the box must avoid the origin and the branch cut: then atan2 is monotone along every edge and its extremes sit in the corners
-    if (!(xl > 0.0f || yl > 0.0f || yh < 0.0f)) return false;
-    const float c0 = fdlibm_atan2f(yl, xl), c1 = fdlibm_atan2f(yl, xh), c2 = fdlibm_atan2f(yh, xl), c3 = fdlibm_atan2f(yh, xh);
-    float a_lo = fminf(fminf(c0, c1), fminf(c2, c3)), a_hi = fmaxf(fmaxf(c0, c1), fmaxf(c2, c3));
-#pragma unroll
-    for (int i = 0; i < 8; i++) { a_lo = f32_step(a_lo, false); a_hi = f32_step(a_hi, true); }    // atan2f's own error (< 2 ulp) at the corners and at the true point, with room for a binade change
-    const int32_t n_lo = fine_from_arg(fine_old, a_lo), n_hi = fine_from_arg(fine_old, a_hi);
-    fine_new = n_lo;
-    return n_lo == n_hi;
 }
 
 // What a window search starts from: the members of RxState the tracking loop reads and writes.
@@ -139,6 +62,8 @@ __device__ __forceinline__ SyncIn sync_in_of(const State& g)
 // (int16)(0.1 x the residual offset in Hz): zero once the residual is below 10 Hz, ofdm-processor.cpp:450-451).  Then every frame
 // pulls exactly T_F samples at coarse + fine Hz.  k_sync_validate walks the frames in order and accepts a frame only if the state
 // its predecessors REALLY left equals the one it was computed from; the rest of the batch goes through the serial chain.
+// (n times the single-frame rule below -- frame_end_pos, frame_null_L, frame_end_phase -- with start_index = T_g and f_prs = f_sym =
+// null_f = coarse + fine: T_u + T_g + 75 T_s + T_null = T_F samples, all at one frequency, so the phase falls by T_F (coarse + fine).)
 __device__ __forceinline__ SyncIn sync_predict(const SyncIn& base, int n)
 {
     SyncIn s = base;
@@ -159,12 +84,20 @@ __device__ __forceinline__ FrameDesc desc_begin(const SyncIn& st)
 // samples a window search needs in the ring: a whole frame with the largest possible window index
 constexpr int64_t SYNC_NEED = (int64_t)T_U + (T_U - 1) + 75 * (int64_t)T_S + T_NULL;
 
+// Where a frame ends, stated once: a window search at d.pos pulls T_u + start_index samples (ofdm-processor.cpp:337,372-374), then 75
+// symbols at f_sym (:432-434), then the null symbol at null_f (:462-463).  The serial chain (finish_desc, state_advance) and the
+// find chain's hand-over (chain_hand_over) take the next search position and the oscillator phases from here; sync_predict is their
+// closed form for n frames in lock.
+__device__ __forceinline__ int64_t frame_end_pos(const FrameDesc& d) { return d.pos + (int64_t)d.start_index + T_U + 75 * (int64_t)T_S + T_NULL; }
+__device__ __forceinline__ int32_t frame_null_L(const FrameDesc& d) { return mod_rate64((int64_t)d.L1 - (int64_t)75 * T_S * d.f_sym); }                  // phase in front of the null symbol
+__device__ __forceinline__ int32_t frame_end_phase(const FrameDesc& d) { return mod_rate64((int64_t)d.null_L - (int64_t)T_NULL * d.null_f); }           // ... and behind it (finished descriptor)
+
 // ofdm-processor.cpp:447-490 in two halves.  finish_desc: the new fine corrector completes the frame's descriptor (the null symbol,
 // :462-463, is pulled with it).  state_advance: what the frame leaves in the receiver state, from its finished descriptor alone.
 __device__ __forceinline__ void finish_desc(FrameDesc& d, int32_t fine)
 {
     const int32_t coarse = d.coarse_after;                            // after the coarse corrector of this frame
-    d.null_L = mod_rate64((int64_t)d.L1 - (int64_t)75 * T_S * d.f_sym);
+    d.null_L = frame_null_L(d);
     d.null_f = coarse + fine;
     d.fine_after = fine; d.coarse_after = coarse;                     // as RadioControllerInterface sees them after the frame
     d.valid = 1;
@@ -177,9 +110,20 @@ __device__ __forceinline__ void state_advance(const SyncArgs& A, const int b, St
     else if (fine < -1000 / 2) { coarse -= 1000; fine += 1000; }
     hist_append(A, b, st, d);
     st.calm_frames = d.start_index == T_G ? (st.calm_frames < (1 << 20) ? st.calm_frames + 1 : st.calm_frames) : 0;
-    st.pos = d.pos + (int64_t)d.start_index + T_U + 75 * (int64_t)T_S + T_NULL;
-    st.local_phase = mod_rate64((int64_t)d.null_L - (int64_t)T_NULL * d.null_f);
+    st.pos = frame_end_pos(d);
+    st.local_phase = frame_end_phase(d);
     st.coarse = coarse; st.fine = fine; st.frame_no = d.frame_no + 1;
+}
+// The find chain's hand-over: the state the NEXT search starts from if this (pending) frame's fine corrector stays where it is --
+// finish_desc with the corrector the frame was searched with, then what state_advance takes from the result; the corrector is handed
+// on unmoved (no +-500 Hz wrap).  k_sync_validate_chain checks exactly that against what k_sync_finish really decided.
+__device__ __forceinline__ void chain_hand_over(SyncIn& st, const FrameDesc& pending)
+{
+    FrameDesc d = pending;
+    finish_desc(d, st.fine);
+    st.pos = frame_end_pos(d);
+    st.local_phase = frame_end_phase(d);
+    st.coarse = d.coarse_after; st.frame_no = d.frame_no + 1;
 }
 
 template <bool WIDE>
@@ -398,6 +342,12 @@ __global__ void __launch_bounds__(FINISH_THREADS, SYNC_FINISH_WIDE_OCC) k_sync_f
     sync_finish_body<true>(A, blockIdx.y, blockIdx.x);
 }
 
+// OFDMProcessor::sLevel = 0.00001 * l1norm(sample) + (1 - 0.00001) * sLevel (ofdm-processor.cpp:174,216): a double expression rounded to
+// float once per sample.  slevel_step(slevel_in(a), level) is that one recurrence; it comes in two parts only so that a replay can
+// form the products ahead of the dependent chain.
+__device__ __forceinline__ double slevel_in(float a) { return 0.00001 * (double)a; }
+__device__ __forceinline__ float slevel_step(double in, float level) { return (float)(in + (1 - 0.00001) * (double)level); }
+
 // ---- sLevel catches up with the samples that were pulled while tracking (ofdm-processor.cpp:216: once per sample, float result
 // of a double expression).  Exact when the history reaches back to the last point at which the level was exact; otherwise two
 // runs from the extremes of what the level can be bracket it (the update is monotone in the level): if they have met by the end,
@@ -442,17 +392,17 @@ __device__ __forceinline__ void slevel_replay(const SyncArgs& A, const int b, Rx
                         const float v[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
                         double a[16];
 #pragma unroll
-                        for (int k = 0; k < 16; k++) a[k] = 0.00001 * (double)v[k];
+                        for (int k = 0; k < 16; k++) a[k] = slevel_in(v[k]);
 #pragma unroll
                         for (int k = 0; k < 16; k++) {
-                            lo = (float)(a[k] + (1 - 0.00001) * (double)lo);
-                            if (!one) hi = (float)(a[k] + (1 - 0.00001) * (double)hi);
+                            lo = slevel_step(a[k], lo);
+                            if (!one) hi = slevel_step(a[k], hi);
                         }
                     }
                     for (; i < m; i++) {
-                        const double a = 0.00001 * (double)l1[i];
-                        lo = (float)(a + (1 - 0.00001) * (double)lo);
-                        if (!one) hi = (float)(a + (1 - 0.00001) * (double)hi);
+                        const double a = slevel_in(l1[i]);
+                        lo = slevel_step(a, lo);
+                        if (!one) hi = slevel_step(a, hi);
                     }
                     if (one) hi = lo;
                     s_lo = lo; s_hi = hi;
@@ -507,7 +457,7 @@ __device__ __forceinline__ void acquire_body(const SyncArgs& A, const int b, flo
                 if (ph == 3 && !((double)(cs / 50) < 0.75 * (double)sLevel)) { done = true; break; }
                 if (i >= (int)avail) break;
                 const float a = l1[i++];
-                sLevel = (float)(0.00001 * (double)a + (1 - 0.00001) * (double)sLevel);         // :174
+                sLevel = slevel_step(slevel_in(a), sLevel);                                     // :174
                 if (ph == 0) {                                                                  // :252-255
                     if (--left <= 0) { ph = 1; idx = 0; cs = 0.0f; st.attempts += 1; }                  // falls through into notSynced (:256)
                 } else if (ph == 1) {                                                           // :268-273
@@ -537,36 +487,63 @@ __device__ __forceinline__ void acquire_body(const SyncArgs& A, const int b, flo
     __syncthreads();                                     // the caller re-reads the state from memory
 }
 
-// stand-alone acquisition launch (no longer part of the frame chain; kept for diagnostics)
-__global__ void __launch_bounds__(256) k_acquire(SyncArgs A)
+// notSynced: the null-symbol search first (ofdm-processor.cpp:256-319).  The FFT tile is free until the window search: it holds the
+// sample tile and the state.
+constexpr int FIND_TILE = T_U + 96;                                  // cf32 entries of sync_find_body's FFT tile
+__device__ __forceinline__ void acquire_in_tile(const SyncArgs& A, const int b, cf32* tile, int& s_done, const int t)
 {
-    __shared__ __attribute__((aligned(16))) float l1[ACQ_TILE];
-    __shared__ RxState s_st;
-    __shared__ int s_done;
-    if (A.state[blockIdx.x].synced) return;
-    acquire_body<256>(A, blockIdx.x, l1, s_st, s_done, threadIdx.x);
+    static_assert(FIND_TILE * sizeof(cf32) >= ACQ_TILE * sizeof(float) + sizeof(RxState) + 16, "acquisition scratch must fit the FFT tile");
+    float* const l1 = reinterpret_cast<float*>(tile);
+    RxState& s_st = *reinterpret_cast<RxState*>(l1 + ACQ_TILE);
+    acquire_body<FFT_THREADS>(A, b, l1, s_st, s_done, t);
 }
 
+// ofdm-processor.cpp:347-350: SyncOnPhase failed -> notSynced (the 2048 samples are consumed).  A wide or find-chain slot that fails
+// only says so in its descriptor and is left to the serial chain (k_sync_validate).
+template <bool WIDE>
+__device__ __forceinline__ void search_failed(const SyncArgs& A, const int b, FrameDesc& d, FrameDesc& dout, const int t)
+{
+    if (t != 0) return;
+    d.valid = 3;
+    dout = d;
+    if (!WIDE) {
+        RxState& g = A.state[b];
+        g.pos = d.pos + T_U;
+        g.local_phase = mod_rate64((int64_t)d.L0 - (int64_t)T_U * d.f_prs);
+        g.synced = 0; g.lost = g.lost + 1; g.attempts = g.attempts + 1;                  // goto notSynced (:347-350 -> :256-262)
+        hist_append(A, b, g, d);                   // the T_u samples of the failed attempt were pulled too
+    }
+}
+
+#ifdef SYNC_CHAIN_TS
+// (timing experiment: where a window search of the find chain spends its time beside the decoder -- 100 MHz stamps of ensemble 0's searches,
+// printed when the handle is destroyed with DABPHY_CHAIN_TS set; build with EXTRA="-DDABPHY_EXPERIMENTS -DSYNC_CHAIN_TS")
+__device__ unsigned long long g_chain_ts[64][8];
+#endif
+// stamp point k of the search that fills slot `slot` (< 0: not timed); nothing in a build without SYNC_CHAIN_TS
+struct ChainStamp {
+    int slot;
+    __device__ __forceinline__ void operator()(int k) const
+    {
+#ifdef SYNC_CHAIN_TS
+        if (slot >= 0 && threadIdx.x == 0) g_chain_ts[slot][k] = wall_clock64();
+#endif
+    }
+};
+
+// One window search, OFDMProcessor::run from SyncOnPhase to the coarse corrector (ofdm-processor.cpp:324-409).
 // MODE 0: the serial chain (the state in HBM is the truth: acquisition first where needed, a failed search falls back to notSynced);
 // MODE 1: the wide pass (frame n from the state sync_predict gives it); MODE 2: the find chain (k_sync_find_chain: the caller hands in the
 // state the frame starts from and, when the search succeeded, gets back the state the NEXT frame starts from if the fine corrector does not
 // move).  Returns true when the descriptor is left pending (valid = 2) for k_sync_finish.
 constexpr int SYNC_CALM_MIN = 8;
 constexpr int SYNC_CHAIN_ROUNDS = 3;
-#ifdef SYNC_CHAIN_TS
-// (timing experiment: where a window search of the find chain spends its time beside the decoder -- 100 MHz stamps of ensemble 0's searches,
-// printed when the handle is destroyed with DABPHY_CHAIN_TS set; build with EXTRA="-DDABPHY_EXPERIMENTS -DSYNC_CHAIN_TS")
-__device__ unsigned long long g_chain_ts[64][8];
-#define CHAIN_TS(k) do { if (MODE == 2 && b == 0 && threadIdx.x == 0) g_chain_ts[frame & 63][k] = wall_clock64(); } while (0)
-#else
-#define CHAIN_TS(k) do { } while (0)
-#endif
 template <int MODE>
 __device__ __forceinline__ bool sync_find_body(const SyncArgs& A, const int b, const int frame, SyncIn& chain_st)
 {
     constexpr bool WIDE = MODE != 0;
     // 17 KiB of LDS, reused phase by phase (FFT tile -> |IFFT| + window maxima)
-    __shared__ __attribute__((aligned(16))) cf32 tile[T_U + 96];
+    __shared__ __attribute__((aligned(16))) cf32 tile[FIND_TILE];
     float* const lbuf = reinterpret_cast<float*>(tile);              // [T_U + 128], valid after the inverse transform
     float* const pa = lbuf + (T_U + 128);                            // [T_U]
     __shared__ float redf[FFT_THREADS];
@@ -575,176 +552,45 @@ __device__ __forceinline__ bool sync_find_body(const SyncArgs& A, const int b, c
     __shared__ __attribute__((aligned(16))) cf32 twB[FFT_TWB_ENTRIES];
     const int t = threadIdx.x;
     const cf32* __restrict__ iq = A.iq + (size_t)b * A.iq_stride;
-    const cf32* __restrict__ nco = A.tab.nco;
-    if (!WIDE && !A.state[b].synced) {
-        // notSynced: null-symbol search first (the FFT tile is free until the window search: it holds the sample tile and the state)
-        static_assert(sizeof(tile) >= ACQ_TILE * sizeof(float) + sizeof(RxState) + 16, "acquisition scratch must fit the FFT tile");
-        float* const l1 = reinterpret_cast<float*>(tile);
-        RxState& s_st = *reinterpret_cast<RxState*>(l1 + ACQ_TILE);
-        acquire_body<FFT_THREADS>(A, b, l1, s_st, redi[0], t);
-    }
+    const ChainStamp ts{MODE == 2 && b == 0 ? (frame & 63) : -1};
+
+    // 1. acquisition, where needed
+    if (!WIDE && !A.state[b].synced) acquire_in_tile(A, b, tile, redi[0], t);
+
+    // 2. the start state
     const SyncIn st = MODE == 2 ? chain_st : MODE == 1 ? sync_predict(sync_in_of(A.state[b]), frame) : sync_in_of(A.state[b]);
     FrameDesc& dout = A.desc[(size_t)b * A.n_frames + frame];
     FrameDesc d = desc_begin(st);
 
-    // a whole frame (with the largest possible window index) must be available
+    // 3. early outs.  A whole frame (with the largest possible window index) must be available
     if (!st.synced || (!A.loop && st.pos + SYNC_NEED > A.n_valid)) {
         if (t == 0) dout = d;
         return false;
     }
-    // the wide pass leaves an ensemble whose window is moving to the find chain: its predicted positions would be wrong from the first
-    // slip on (k_sync_validate then stops at this slot, which keeps valid = 0)
+    // ... and the wide pass leaves an ensemble whose window is moving to the find chain: its predicted positions would be wrong from the
+    // first slip on (k_sync_validate then stops at this slot, which keeps valid = 0)
     if (MODE == 1 && A.state[b].calm_frames < SYNC_CALM_MIN) {
         if (t == 0) dout = d;
         return false;
     }
 
-    CHAIN_TS(0);
+    // 4. the impulse response
+    ts(0);
     FftTwiddles w; fft_load_twiddles(w, A.tab.tw, twB, t);
-    cf32 v[16], u[16];
-    // ---- PhaseReference::findIndex (phasereference.cpp:73-92): FFT, multiply by conj(refTable), IFFT (scaled by 1/N)
-    load_mix2048(v, iq, A.ring, st.pos, 0, nco, d.L0, d.f_prs, 0, t);
-#ifdef SYNC_CHAIN_TS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    CHAIN_TS(1);
-    fft2048_wg<false>(v, tile, w, t);
-    CHAIN_TS(2);
-#pragma unroll
-    for (int j = 0; j < 16; j++) v[j] = cmul(v[j], cconj(A.tab.ref[t + 128 * j]));
-#pragma unroll
-    for (int h = 0; h < 2; h++)
-#pragma unroll
-        for (int j = 0; j < 8; j++) u[8 * h + j] = v[h + 2 * j];          // bin t + 128 (h + 2j) = input t + 128h + 256j
-    fft2048_wg<true>(u, tile, w, t);
-    CHAIN_TS(3);
-    __syncthreads();                                                       // all round-C reads of the tile are done: it becomes lbuf / pa
-    const float factor = 1.0f / (float)T_U;                                // fft.cpp:154
-    float* cir = A.cir ? A.cir + ((size_t)b * A.n_frames + frame) * T_U : nullptr;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const float a = hypotf_exact(u[j].re * factor, u[j].im * factor);  // phasereference.cpp:214-215
-        lbuf[t + 128 * j] = a;
-        if (cir) cir[t + 128 * j] = a;
-    }
-    if (t < 128) lbuf[T_U + t] = 0.0f;
-    __syncthreads();
-    CHAIN_TS(4);
+    float* const cir = A.cir ? A.cir + ((size_t)b * A.n_frames + frame) * T_U : nullptr;
+    prs_impulse_response(A, iq, d, w, tile, lbuf, cir, t, ts);
 
+    // 5. the window index by the selected FFTPlacementMethod
     int startIndex = -1;
-    if (A.fft_placement == 0) {
-        // StrongestPeak (phasereference.cpp:99-129): sum in order, first maximum
-        if (t == 0) { float s = 0; for (int i = 0; i < T_U; i++) s += lbuf[i]; s_sum = s; }
-        float mx = -10000.0f;
-#pragma unroll
-        for (int j = 0; j < 16; j++) mx = fmaxf(mx, lbuf[16 * t + j]);
-        const float gmax = block_max(mx, redf, t);
-        int cand = T_U;
-        for (int j = 15; j >= 0; j--) if (lbuf[16 * t + j] == gmax) cand = 16 * t + j;
-        const int first = block_min_int(cand, redi, t);
-        const float sum = s_sum;
-        if (sum == 0) startIndex = -1;
-        else if (gmax < 3 * sum / T_U) startIndex = (int)(-fabsf(gmax * T_U / sum) - 1);
-        else startIndex = first;
-    } else if (A.fft_placement == 1) {
-        // EarliestPeakWithBinning (phasereference.cpp:125-211): peaks over 102 bins of 20 samples (2040..2047 are never
-        // looked at), the highest peak, the 4 highest bins within 500 samples of it, those above 3 * mean, the earliest.
-        float* const bval = pa; int* const bidx = reinterpret_cast<int*>(pa + 128);
-        if (t == 0) { float s = 0; for (int i = 0; i < 2040; i++) s += lbuf[i]; s_sum = s; }    // `mean += value` in index order
-        if (t < 102) {
-            float pv = 0.0f; int pi = -1;
-            for (int j = 0; j < 20; j++) { const float v2 = lbuf[20 * t + j]; if (v2 > pv) { pv = v2; pi = 20 * t + j; } }
-            bval[t] = pv; bidx[t] = pi;
-        }
-        if (cir && t < 8) cir[2040 + t] = 0.0f;                                                  // the reference's buffer keeps its zeros there
-        __syncthreads();
-        if (t == 0) {
-            const float mean = s_sum / T_U;
-            // std::sort by value (descending) is replaced by selection: the order among exactly equal peaks is the bin order
-            int top = 0;
-            for (int k = 1; k < 102; k++) if (bval[k] > bval[top]) top = k;
-            const int peak_index = bidx[top];
-            unsigned long long used_lo = 0, used_hi = 0;
-            int found = 0, mn = 0;
-            for (int pass = 0; pass < 4; pass++) {
-                int best = -1;
-                for (int k = 0; k < 102; k++) {
-                    const bool used = k < 64 ? (used_lo >> k) & 1 : (used_hi >> (k - 64)) & 1;
-                    const int dist = bidx[k] - peak_index;
-                    if (used || (dist < 0 ? -dist : dist) > 500) continue;
-                    if (best < 0 || bval[k] > bval[best]) best = k;
-                }
-                if (best < 0) break;
-                if (best < 64) used_lo |= 1ull << best; else used_hi |= 1ull << (best - 64);
-                if (bval[best] < 3 * mean) continue;
-                if (!found || bidx[best] < mn) { mn = bidx[best]; found = 1; }
-            }
-            redi[0] = found ? mn : -1;
-        }
-        __syncthreads();
-        startIndex = redi[0];
-        __syncthreads();
-    } else {
-        // ThresholdBeforePeak (phasereference.cpp:212-252)
-        if (t == 0) {                                                                          // :214-218, in order
-            float s = 0; const float4* l4 = reinterpret_cast<const float4*>(lbuf);
-            for (int i = 0; i < T_U / 4; i += 4) {
-                const float4 q0 = l4[i], q1 = l4[i + 1], q2 = l4[i + 2], q3 = l4[i + 3];
-                s += q0.x; s += q0.y; s += q0.z; s += q0.w; s += q1.x; s += q1.y; s += q1.z; s += q1.w;
-                s += q2.x; s += q2.y; s += q2.z; s += q2.w; s += q3.x; s += q3.y; s += q3.z; s += q3.w;
-            }
-            s_sum = s;
-        }
-        // peak_averages[i] = max(lbuf[i .. i+99]) for i < 1948; thread t owns i = 16t .. 16t+15
-        float mx = -10000.0f;
-        if (16 * t < T_U - 100) {
-            float common = -10000.0f;                                   // lbuf[16t+15 .. 16t+99]
-            for (int k = 16 * t + 15; k <= 16 * t + 99; k++) common = fmaxf(common, lbuf[k]);
-            float suf[16];                                              // suf[k] = max(lbuf[16t+k .. 16t+14])
-            float run = -10000.0f;
-#pragma unroll
-            for (int k = 14; k >= 0; k--) { run = fmaxf(run, lbuf[16 * t + k]); suf[k] = run; }
-            suf[15] = -10000.0f;
-            run = -10000.0f;                                            // prefix over lbuf[16t+100 .. 16t+99+k]
-#pragma unroll
-            for (int k = 0; k < 16; k++) {
-                const int i = 16 * t + k;
-                if (k > 0) run = fmaxf(run, lbuf[16 * t + 99 + k]);
-                float m = fmaxf(common, suf[k]);
-                if (k > 0) m = fmaxf(m, run);
-                if (i + 100 < T_U) { pa[i] = m; mx = fmaxf(mx, m); } else pa[i] = 0.0f;
-            }
-        } else {
-            for (int k = 0; k < 16; k++) pa[16 * t + k] = 0.0f;
-        }
-        const float gmax = block_max(mx, redf, t);                       // contains the barriers that publish pa / s_sum
-        const float sum = s_sum;
-        int cand = T_U;
-        if (gmax > 3 * sum / T_U) {                                      // :238-239
-            const float thresh = gmax / 2;
-            for (int k = 15; k >= 0; k--) {
-                const int i = 16 * t + k;
-                if (i + 100 < T_U && pa[i + 100] > thresh) cand = i;    // :241-245
-            }
-        }
-        const int first = block_min_int(cand, redi, t);
-        startIndex = first < T_U ? first : -1;
-    }
+    if (A.fft_placement == 0) startIndex = window_strongest_peak(lbuf, redf, redi, &s_sum, t);
+    else if (A.fft_placement == 1) startIndex = window_earliest_peak_binned(lbuf, pa, redi, &s_sum, cir, t);
+    else startIndex = window_threshold_before_peak(lbuf, pa, redf, redi, &s_sum, t);
+    ts(5);
 
-    CHAIN_TS(5);
+    // 6. failed -> not synced
     if (startIndex < 0) {
-        // ofdm-processor.cpp:347-350: SyncOnPhase failed -> notSynced (the 2048 samples are consumed)
-        if (t == 0) {
-            d.start_index = startIndex; d.valid = 3;   // window search failed: SyncOnPhase -> notSynced
-            dout = d;
-        }
-        if (!WIDE && t == 0) {                         // (a wide slot that fails is left to the serial chain: k_sync_validate)
-            RxState& g = A.state[b];
-            g.pos = st.pos + T_U;
-            g.local_phase = mod_rate64((int64_t)d.L0 - (int64_t)T_U * d.f_prs);
-            g.synced = 0; g.lost = g.lost + 1; g.attempts = g.attempts + 1;                  // goto notSynced (:347-350 -> :256-262)
-            hist_append(A, b, g, d);                   // the T_u samples of the failed attempt were pulled too
-        }
+        d.start_index = startIndex;
+        search_failed<WIDE>(A, b, d, dout, t);
         return false;
     }
     d.start_index = startIndex;
@@ -752,7 +598,12 @@ __device__ __forceinline__ bool sync_find_body(const SyncArgs& A, const int b, c
     const int32_t J0 = startIndex + T_U;
     d.L1 = mod_rate64((int64_t)d.L0 - (int64_t)J0 * d.f_prs);
 
-    // ---- coarse frequency corrector (ofdm-processor.cpp:397-409, processPRS :537-616 PatternOfZeros)
+    // 7. the coarse corrector (ofdm-processor.cpp:397-409, processPRS :537-644).  NOT yet split into one function per FreqsyncMethod: three
+    // forms of that split (methods inlined; PatternOfZeros' carrier argument out of line; the three methods out of line) each made the
+    // compiler schedule the window search above differently, and each measured 0.4 - 1.3 % slower on the headline than this inline form,
+    // which measures level with the parent (profiles/sync_steps_ab.txt, "functions against inline")
+    cf32 v[16];
+    const cf32* __restrict__ nco = A.tab.nco;
     int32_t coarse = st.coarse;
     if (!A.disable_coarse && A.dec[b].fic_ratio * 10 < 50) {
         d.coarse_ran = 1;
@@ -810,55 +661,51 @@ __device__ __forceinline__ bool sync_find_body(const SyncArgs& A, const int b, c
                 if (abs(coarse) > 35000) coarse = 0;
             }
         } else {
-        float sum = 3.0e38f; int idx = 1 << 20;
-        if (t < 72) {
-            const int i = T_U - 36 + t;
+            float sum = 3.0e38f; int idx = 1 << 20;
+            if (t < 72) {
+                const int i = T_U - 36 + t;
 #define FB(k) tile[(k) % T_U]
 #define ARG(a, c) ([&] { const cf32 z_ = cmul(FB(a), cconj(FB(c))); return fdlibm_atan2f(z_.im, z_.re); }())
-            // the reference's unqualified abs() binds to ::abs(int): arguments are truncated to int first
-            // (disassembly of the -O2 build: cvttsd2si / cvttss2si); oracle/dabphy_oracle.c pins this.
-            const float a1 = (float)abs(abs((int)((double)ARG(i + 1, i + 2) / M_PI)) - 1);
-            const float a2 = (float)abs(abs((int)((double)ARG(i + 2, i + 3) / M_PI)) - 1);
-            const float a3 = (float)abs((int)ARG(i + 3, i + 4));
-            const float a4 = (float)abs((int)ARG(i + 4, i + 5));
-            const float a5 = (float)abs((int)ARG(i + 5, i + 6));
-            const float b1 = (float)abs(abs((int)((double)ARG(i + 17, i + 19) / M_PI)) - 1);
-            const float b2 = (float)abs((int)ARG(i + 19, i + 20));
-            const float b3 = (float)abs((int)ARG(i + 20, i + 21));
-            const float b4 = (float)abs((int)ARG(i + 21, i + 22));
+                // the reference's unqualified abs() binds to ::abs(int): arguments are truncated to int first
+                // (disassembly of the -O2 build: cvttsd2si / cvttss2si); oracle/dabphy_oracle.c pins this.
+                const float a1 = (float)abs(abs((int)((double)ARG(i + 1, i + 2) / M_PI)) - 1);
+                const float a2 = (float)abs(abs((int)((double)ARG(i + 2, i + 3) / M_PI)) - 1);
+                const float a3 = (float)abs((int)ARG(i + 3, i + 4));
+                const float a4 = (float)abs((int)ARG(i + 4, i + 5));
+                const float a5 = (float)abs((int)ARG(i + 5, i + 6));
+                const float b1 = (float)abs(abs((int)((double)ARG(i + 17, i + 19) / M_PI)) - 1);
+                const float b2 = (float)abs((int)ARG(i + 19, i + 20));
+                const float b3 = (float)abs((int)ARG(i + 20, i + 21));
+                const float b4 = (float)abs((int)ARG(i + 21, i + 22));
 #undef ARG
 #undef FB
-            sum = a1 + a2 + a3 + a4 + a5 + b1 + b2 + b3 + b4;
-            idx = i;
-        }
-        // first index with the smallest sum (strict '<' scan in ascending i, Mmin starts at 1000)
-        const float neg_min = block_max(-sum, redf, t);
-        const int first = block_min_int((-sum == neg_min) ? idx : (1 << 20), redi, t);
-        {
-            const int index = (-neg_min < 1000.0f) ? first : 100;       // "int16_t index = 100" when nothing beat Mmin = 1000
-            const int correction = index - T_U;
-            if (correction != 100) {                                     // :403 (always true, kept for fidelity)
-                coarse += correction * 1000;
-                if (abs(coarse) > 35000) coarse = 0;
+                sum = a1 + a2 + a3 + a4 + a5 + b1 + b2 + b3 + b4;
+                idx = i;
+            }
+            // first index with the smallest sum (strict '<' scan in ascending i, Mmin starts at 1000)
+            const float neg_min = block_max(-sum, redf, t);
+            const int first = block_min_int((-sum == neg_min) ? idx : (1 << 20), redi, t);
+            {
+                const int index = (-neg_min < 1000.0f) ? first : 100;       // "int16_t index = 100" when nothing beat Mmin = 1000
+                const int correction = index - T_U;
+                if (correction != 100) {                                     // :403 (always true, kept for fidelity)
+                    coarse += correction * 1000;
+                    if (abs(coarse) > 35000) coarse = 0;
+                }
             }
         }
-        }
     }
+
+    // 8. pending descriptor: k_sync_finish completes it
     d.f_sym = coarse + st.fine;
     d.coarse_after = coarse;
     d.coarse_step = coarse - st.coarse;
-    d.valid = 2;                                   // pending: k_sync_finish completes it
+    d.valid = 2;
     if (t == 0) dout = d;
-    if (MODE == 2) {
-        // where the next frame starts if the fine corrector stays where it is (finish_desc + state_advance with fine unchanged;
-        // k_sync_validate_chain checks exactly that against what k_sync_finish really decided)
-        const int32_t null_L = mod_rate64((int64_t)d.L1 - (int64_t)75 * T_S * d.f_sym), null_f = coarse + st.fine;
-        chain_st.pos = d.pos + (int64_t)startIndex + T_U + 75 * (int64_t)T_S + T_NULL;
-        chain_st.frame_no = d.frame_no + 1;
-        chain_st.local_phase = mod_rate64((int64_t)null_L - (int64_t)T_NULL * null_f);
-        chain_st.coarse = coarse;
-    }
-    CHAIN_TS(6);
+
+    // 9. (find chain) the next frame's start
+    if (MODE == 2) chain_hand_over(chain_st, d);
+    ts(6);
     return true;
 }
 
@@ -910,22 +757,34 @@ __global__ void __launch_bounds__(FFT_THREADS, 1) k_sync_find_chain(SyncArgs A) 
 // (the judges walk 32 frames per lane: the members of RxState they touch live in registers meanwhile -- as members of the global struct
 // every frame cost a chain of dependent memory round trips, 93 us per pass on the step's critical path -- and the next descriptor is
 // fetched while the current one is judged)
-struct RxHot {
-    int64_t pos, frame_no; int32_t local_phase, coarse, fine, synced;
+// RxHot: SyncIn plus the counters the judges touch.  hot_store writes back everything but `synced` and `attempts`, which are only read.
+// A new hot member goes into the struct and into the two functions right below it.
+struct RxHot : SyncIn {
     int32_t n_exact_sums, hist_count, hist_head, hist_dropped, attempts, first_lock_attempts, n_wide_frames, n_chain_frames, calm_frames;
 };
+__device__ __forceinline__ RxHot hot_load(const RxState& G)
+{
+    RxHot g;
+    static_cast<SyncIn&>(g) = sync_in_of(G);
+    g.n_exact_sums = G.n_exact_sums; g.hist_count = G.hist_count; g.hist_head = G.hist_head; g.hist_dropped = G.hist_dropped; g.attempts = G.attempts;
+    g.first_lock_attempts = G.first_lock_attempts; g.n_wide_frames = G.n_wide_frames; g.n_chain_frames = G.n_chain_frames; g.calm_frames = G.calm_frames;
+    return g;
+}
+__device__ __forceinline__ void hot_store(RxState& G, const RxHot& g)
+{
+    G.pos = g.pos; G.frame_no = g.frame_no; G.local_phase = g.local_phase; G.coarse = g.coarse; G.fine = g.fine;
+    G.n_exact_sums = g.n_exact_sums; G.hist_count = g.hist_count; G.hist_head = g.hist_head; G.hist_dropped = g.hist_dropped;
+    G.first_lock_attempts = g.first_lock_attempts; G.n_wide_frames = g.n_wide_frames; G.n_chain_frames = g.n_chain_frames; G.calm_frames = g.calm_frames;
+}
 template <bool CHAIN>
 __device__ __forceinline__ void sync_validate_body(const SyncArgs& A)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= A.n_ens) return;
     RxState& G = A.state[b];
-    RxHot g;
-    g.pos = G.pos; g.frame_no = G.frame_no; g.local_phase = G.local_phase; g.coarse = G.coarse; g.fine = G.fine; g.synced = G.synced;
-    g.n_exact_sums = G.n_exact_sums; g.hist_count = G.hist_count; g.hist_head = G.hist_head; g.hist_dropped = G.hist_dropped; g.attempts = G.attempts;
-    g.first_lock_attempts = G.first_lock_attempts; g.n_wide_frames = G.n_wide_frames; g.n_chain_frames = G.n_chain_frames; g.calm_frames = G.calm_frames;
+    RxHot g = hot_load(G);
     FrameDesc* const desc = A.desc + (size_t)b * A.n_frames;
-    const SyncIn base = sync_in_of(g);
+    const SyncIn base = g;
     int n = CHAIN ? A.redo_out[b] : 0;
     if (base.synced && n < A.n_frames) {
         FrameDesc next = desc[n];
@@ -938,7 +797,7 @@ __device__ __forceinline__ void sync_validate_body(const SyncArgs& A)
             }
             if (!A.loop && g.pos + SYNC_NEED > A.n_valid) {
                 // out of samples: this slot and the ones behind it stay empty, as the serial chain leaves them
-                const FrameDesc e = desc_begin(sync_in_of(g));
+                const FrameDesc e = desc_begin(g);
                 for (int m = n; m < A.n_frames; m++) desc[m] = e;
                 n = A.n_frames;
                 break;
@@ -951,9 +810,7 @@ __device__ __forceinline__ void sync_validate_body(const SyncArgs& A)
             g.n_wide_frames += 1;
             if (CHAIN) g.n_chain_frames += 1;
         }
-        G.pos = g.pos; G.frame_no = g.frame_no; G.local_phase = g.local_phase; G.coarse = g.coarse; G.fine = g.fine;
-        G.n_exact_sums = g.n_exact_sums; G.hist_count = g.hist_count; G.hist_head = g.hist_head; G.hist_dropped = g.hist_dropped;
-        G.first_lock_attempts = g.first_lock_attempts; G.n_wide_frames = g.n_wide_frames; G.n_chain_frames = g.n_chain_frames; G.calm_frames = g.calm_frames;
+        hot_store(G, g);
     }
     A.redo_out[b] = n;
     if (CHAIN && A.last_round && n < A.n_frames) *A.any_redo = 1;
@@ -966,14 +823,13 @@ __global__ void __launch_bounds__(64) k_sync_validate_chain(SyncArgs A) { sync_v
 // the single-ensemble real-time receiver, where it is 3 % of a frame's 96 ms) instead of catching up when lock is lost.
 __global__ void __launch_bounds__(256) k_slevel_catchup(SyncArgs A)
 {
-    constexpr int TILE = 1024;
-    __shared__ __attribute__((aligned(16))) float l1[TILE];
+    __shared__ __attribute__((aligned(16))) float l1[ACQ_TILE];
     __shared__ RxState s_st;
     const int t = threadIdx.x, b = blockIdx.x;
     if (t == 0) s_st = A.state[b];
     __syncthreads();
     if (s_st.hist_count == 0 || !A.hist) return;
-    slevel_replay<TILE, 256>(A, b, s_st, l1, A.iq + (size_t)b * A.iq_stride, A.tab.nco, t);
+    slevel_replay<ACQ_TILE, 256>(A, b, s_st, l1, A.iq + (size_t)b * A.iq_stride, A.tab.nco, t);
     if (t == 0) {
         RxState& g = A.state[b];
         g.s_level = s_st.s_level; g.hist_count = 0; g.hist_head = 0; g.hist_dropped = 0; g.n_relock_inexact = s_st.n_relock_inexact;
@@ -1029,10 +885,6 @@ void launch_sync_find(const SyncArgs& a, hipStream_t s)
 void launch_sync_finish(const SyncArgs& a, hipStream_t s)
 {
     hipLaunchKernelGGL(k_sync_finish, dim3(a.n_ens), dim3(FINISH_THREADS), 0, s, a);
-}
-void launch_acquire(const SyncArgs& a, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_acquire, dim3(a.n_ens), dim3(256), 0, s, a);
 }
 
 } // namespace dabphy

@@ -17,7 +17,7 @@ namespace {
 // The sample ring in HBM holds 80 transmission frames (126 MB of a 288 GB device) although the worker only writes kAhead = 8 frames
 // ahead of the synchroniser: the 72 frames behind it are the memory OFDMProcessor::sLevel needs.  The reference advances that level
 // with every sample it pulls (ofdm-processor.cpp:174,216) -- a serial recurrence, 3 ms of one GPU lane per frame -- but reads it
-// only after a loss of lock.  So nothing is spent on it while tracking; at a loss of lock k_acquire replays the samples pulled
+// only after a loss of lock.  So nothing is spent on it while tracking; at a loss of lock k_sync_find's acquisition head (acquire_body) replays the samples pulled
 // since the last acquisition (exactly; up to 64 frames back, beyond that two bracketing replays that meet: DESIGN.md section 7).
 constexpr uint64_t kRing = 80ull * 196608;
 constexpr uint64_t kAhead = 8ull * 196608;

@@ -6,7 +6,7 @@
 // headers (radio-controller.h, fib-processor.h, decoder_adapter.h, dab-constants.h); only the PHY hot path behind them is replaced:
 //
 //   reference object                      replaced by
-//   OFDMProcessor (+PhaseReference)       dabphy_process: k_acquire, k_sync_find, k_sync_finish
+//   OFDMProcessor (+PhaseReference)       dabphy_process: k_sync_find (acquisition head: acquire_body), k_sync_finish
 //   OfdmDecoder                           k_demod, k_snr*
 //   FicHandler (depuncture/Viterbi/CRC)   k_fic_gather, k_viterbi, k_fib_crc        -> FIBProcessor::processFIB stays
 //   MscHandler + DabAudio + Protection    k_msc_gather, k_viterbi                   -> DecoderAdapter::addtoFrame stays
