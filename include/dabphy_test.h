@@ -73,6 +73,27 @@ int dabphy_test_tii_pairs(dabphy_handle* h, const float* null, const float* prs,
  * comb/pattern pairs, since dabphy_set_tii switched the side path on for the first time or the last dabphy_reset. */
 int dabphy_test_tii_dropped(dabphy_handle* h, int32_t* per_ensemble);
 
+/* The PRS window search and the coarse corrector (sync_find_body of k_sync.hip: PhaseReference::findIndex by the handle's fft_placement,
+ * OFDMProcessor::processPRS by its freqsync_method, the gate by its disable_coarse) on host-supplied cases, one per ensemble: ONE of the
+ * launches dabphy_process queues -- kernel = DABPHY_TEST_SYNC_SERIAL (k_sync_find), _WIDE (k_sync_find_wide) or _CHAIN (k_sync_find_chain
+ * from frame 0 on) -- with the arguments dabphy_process gives it, over a looping ring of 2 x DABPHY_TEST_SYNC_CASE samples per ensemble
+ * that holds the case at position 0 and zeros behind it.
+ *   iq [n_ens][DABPHY_TEST_SYNC_CASE] cf32: the search reads samples 0 .. 2047, the coarse corrector 2048 samples from the index found;
+ *   coarse, fine [n_ens]: the correctors the receiver -- in lock, oscillator phase 0 -- starts with (only their sum moves the oscillator:
+ *   coarse + fine = 0 leaves the samples unchanged); fic_ratio [n_ens]: the 0 .. 10 counter the gate `ratio * 10 < 50` consults.
+ * n_frames = 1, or with _CHAIN up to max_frames: frame n + 1 is searched where the hand-over of frame n puts it (the ring index of a
+ * frame's search is that of its predecessor + start_index + 2048 + 75 * 2552 + 2656, modulo the ring).
+ * out [n_ens][n_frames], cir [n_ens][n_frames][2048] (the impulse response magnitudes; zeros where no search ran), state [n_ens]: what
+ * the launch left in the receiver state (a failed serial search consumes 2048 samples and drops lock; _WIDE and _CHAIN leave it alone).
+ * DABPHY_ERR_INVALID, nothing launched: n_ens != the handle's n_ensembles, a null pointer, an unknown kernel, n_frames = 0 or above
+ * max_frames or (not _CHAIN) above 1.  The handle's synchroniser and decoder state are overwritten: dabphy_reset before anything else. */
+#define DABPHY_TEST_SYNC_CASE 4096
+enum { DABPHY_TEST_SYNC_SERIAL = 0, DABPHY_TEST_SYNC_WIDE = 1, DABPHY_TEST_SYNC_CHAIN = 2 };
+typedef struct { int64_t pos; int32_t start_index, valid, coarse_ran, coarse_after, coarse_step, L1; } dabphy_test_sync_desc;   /* FrameDesc members of the same names */
+typedef struct { int64_t pos; int32_t synced, lost; } dabphy_test_sync_state;
+int dabphy_test_sync_find(dabphy_handle* h, int32_t kernel, const float* iq, const int32_t* coarse, const int32_t* fine, const int32_t* fic_ratio,
+                          uint32_t n_ens, uint32_t n_frames, dabphy_test_sync_desc* out, float* cir, dabphy_test_sync_state* state);
+
 /* Unit entry of the access-unit pack pass (k_au_pack, the launch behind every filter pass while dabphy_set_au_drain is on) on host-supplied
  * corrected superframes and their events, treated as ONE service: sf [n_sf][120 * s_per_sf], events [n_events] as the filter writes them
  * (sf_slot = index into sf, au_crc_ok as it stands: no CRC is checked here), format = DABPHY_AU_RAW / DABPHY_AU_LOAS.  out [out_capacity]

@@ -196,6 +196,8 @@ void orc_fft2048(const orc_cf32* in, orc_cf32* out, int inverse)
 
 /* ------------------------------------------------------------------------------------------ time sync */
 
+void orc_std_sort_desc(const float* value, const int* index, int n, int* order);     /* oracle/sort_order.cpp */
+
 /* phasereference.cpp:73-256 */
 int orc_find_index(const orc_cf32* v, int method, float* impulse)
 {
@@ -231,9 +233,8 @@ int orc_find_index(const orc_cf32* v, int method, float* impulse)
         }
         for (int i = BIN * NB; i < ORC_TU; i++) ir[i] = 0;          /* the member buffer keeps its initial zeros there */
         mean /= ORC_TU;
-        /* std::sort by value, descending (ties -- exact float equality of two bin maxima -- in bin order here) */
-        for (int k = 0; k < NB; k++) order[k] = k;
-        for (int a = 1; a < NB; a++) { int o = order[a], bpos = a; while (bpos > 0 && val[order[bpos - 1]] < val[o]) { order[bpos] = order[bpos - 1]; bpos--; } order[bpos] = o; }
+        /* std::sort by value, descending: the library's own sort decides the order among bit-identical bin maxima (oracle/sort_order.cpp) */
+        orc_std_sort_desc(val, idx, NB, order);
         const int peak_index = idx[order[0]];
         /* not farther than 500 from the highest peak, then the 4 highest, then those above 3 * mean; min_element over the
          * survivors (an all-zero input leaves bins of index -1 that survive: 0 < 0 is false) */

@@ -2299,5 +2299,183 @@ def check_tii_pairs_small_output(d_factory):
         d.close()
 
 
+# ---- the synchroniser's two decisions, case by case: the PRS window search and the coarse corrector of sync_find_body (k_sync.hip) through
+# dabphy_test_sync_find on the directed inputs of tests/sync_cases.py, against the restatement's findIndex / processPRS on the same samples.
+# Integers are compared exactly, impulse responses bit for bit: no tolerance anywhere.
+SYNC_BATCH = 64                    # cases per launch, one ensemble each
+SYNC_KERNELS = {"serial": 0, "wide": 1, "chain": 2}       # k_sync_find, k_sync_find_wide, k_sync_find_chain
+
+
+def sync_cases():
+    import sync_cases as SC        # (its import runs the restatement over every case list: not at this module's import, smoke() loads it too)
+    return SC
+
+
+def sync_run(d, kernel, iq, coarse, fine, ratio, n_frames=1):
+    """the cases in launches of the handle's n_ensembles (the last one filled up with all-zero cases) -> desc [n][F], cir [n][F][2048], state [n]"""
+    B = d.cfg.n_ensembles
+    iq = np.ascontiguousarray(iq, np.complex64).reshape(-1, 4096); n = len(iq)
+    par = [np.asarray(a, np.int32).reshape(-1) for a in (coarse, fine, ratio)]
+    desc, cir, st = [], [], []
+    for i in range(0, n, B):
+        k = min(B, n - i)
+        q = np.zeros((B, 4096), np.complex64); q[:k] = iq[i:i + k]
+        p = [np.concatenate([a[i:i + k], np.zeros(B - k, np.int32)]) for a in par]
+        de, ci, s = d.test_sync_find(kernel, q, p[0], p[1], p[2], n_frames)
+        desc.append(de[:k]); cir.append(ci[:k]); st.append(s[:k])
+    return np.concatenate(desc), np.concatenate(cir), np.concatenate(st)
+
+
+def sync_assert_state(kernel, st, failed, names):
+    """what the launch leaves in the receiver state: a failed SERIAL search consumes T_u samples and drops lock (ofdm-processor.cpp:347-350);
+    the wide pass and the find chain only report (valid = 3) and leave the state to the serial chain"""
+    for i, name in enumerate(names):
+        want = (2048, 0, 1) if (kernel == SYNC_KERNELS["serial"] and failed[i]) else (0, 1, 0)
+        got = (int(st[i]["pos"]), int(st[i]["synced"]), int(st[i]["lost"]))
+        assert got == want, "%s: state (pos, synced, lost) = %s, expected %s" % (name, got, want)
+
+
+def sync_assert_search(name, de, ci, want_idx, want_ir, pos=0):
+    got = int(de["start_index"])
+    assert got == want_idx, "%s: start_index %d, expected %d" % (name, got, want_idx)
+    diff = np.flatnonzero(ci.view(np.uint32) != want_ir.view(np.uint32))
+    assert len(diff) == 0, "%s: %d impulse response values differ, first at %d: %r / %r" % (name, len(diff), diff[0], ci[diff[0]], want_ir[diff[0]])
+    assert int(de["valid"]) == (2 if want_idx >= 0 else 3) and int(de["pos"]) == pos and int(de["L1"]) == 0, (name, de)
+
+
+def check_sync_cases_window(d_factory, kernel_name, methods=None):
+    """every window case against all three FFTPlacementMethods through one kernel; the coarse gate stays closed (FIC ratio 10)"""
+    SC = sync_cases()
+    kernel = SYNC_KERNELS[kernel_name]
+    cases = SC.WINDOW_CASES
+    iq = np.stack([c.iq for c in cases]); n = len(cases)
+    zero = np.zeros(n, np.int32)
+    for m in (SC.METHODS if methods is None else methods):
+        d = d_factory(n_ensembles=SYNC_BATCH, max_frames=1, fft_placement=m, want_constellation=False)
+        try:
+            desc, cir, st = sync_run(d, kernel, iq, zero, zero, zero + 10)
+        finally:
+            d.close()
+        want = SC.ORACLE_WINDOW[m]
+        for i, c in enumerate(cases):
+            name = "%s, placement %d, %s" % (c.name, m, kernel_name)
+            sync_assert_search(name, desc[i, 0], cir[i, 0], want[i][0], want[i][1])
+            assert (int(desc[i, 0]["coarse_ran"]), int(desc[i, 0]["coarse_after"]), int(desc[i, 0]["coarse_step"])) == (0, 0, 0), (name, desc[i, 0])
+        sync_assert_state(kernel, st, [w[0] < 0 for w in want], ["%s, placement %d, %s" % (c.name, m, kernel_name) for c in cases])
+
+
+def sync_coarse_list(d_factory, kernel_name, cases, oracle, placement, fm, disable):
+    """one coarse list through one kernel with one configuration; oracle[i] = (start_index, correction or None, coarse_after) of the restatement"""
+    kernel = SYNC_KERNELS[kernel_name]
+    iq = np.stack([c.iq for c in cases])
+    coarse = np.array([c.coarse for c in cases], np.int32); fine = np.array([c.fine for c in cases], np.int32); ratio = np.array([c.ratio for c in cases], np.int32)
+    assert ((coarse + fine) == 0).all()                         # the oscillator stays at 1 + 0j: mixing is the stream tests' business
+    d = d_factory(n_ensembles=min(SYNC_BATCH, len(cases)), max_frames=1, fft_placement=placement, freqsync_method=fm, disable_coarse=disable, want_constellation=False)
+    try:
+        desc, cir, st = sync_run(d, kernel, iq, coarse, fine, ratio)
+    finally:
+        d.close()
+    for i, c in enumerate(cases):
+        s, corr, after = oracle[i]
+        ran = corr is not None and not disable
+        if not ran:
+            after = c.coarse
+        de = desc[i, 0]
+        name = "%s, placement %d, freqsync %d%s, %s" % (c.name, placement, fm, ", coarse corrector disabled" if disable else "", kernel_name)
+        got = (int(de["start_index"]), int(de["coarse_ran"]), int(de["coarse_after"]), int(de["coarse_step"]), int(de["valid"]), int(de["L1"]), int(de["pos"]))
+        assert got == (s, int(ran), after, after - c.coarse, 2, 0, 0), "%s: %s, expected %s (correction %s)" % (name, got, (s, int(ran), after, after - c.coarse, 2, 0, 0), corr)
+    sync_assert_state(kernel, st, [False] * len(cases), [c.name for c in cases])
+
+
+def check_sync_cases_coarse(d_factory, kernel_name, freqsync=None):
+    """every coarse case against all three FreqsyncMethods through one kernel (placement: StrongestPeak, see tests/sync_cases.py), and once
+    more with disableCoarseCorrector; then the receiver-layout cases under all three placement methods, which take the coarse window at
+    other, mostly odd places.  Expected: the restatement's processPRS on the 2048 samples at the index found, applied by
+    sync_cases.coarse_rule -- the one statement of `coarse += c * 1000; |coarse| > 35 000 -> 0`."""
+    SC = sync_cases()
+    for fm in (SC.FREQSYNC if freqsync is None else freqsync):
+        for disable in (False, True):
+            sync_coarse_list(d_factory, kernel_name, SC.COARSE_CASES, SC.ORACLE_COARSE[fm], SC.COARSE_PLACEMENT, fm, disable)
+        for m in SC.METHODS:
+            sync_coarse_list(d_factory, kernel_name, SC.RECEIVER_CASES, SC.ORACLE_RECEIVER[m][fm], m, fm, False)
+
+
+def check_sync_cases_two_frames(d_factory):
+    """the find chain over two frames per ensemble: the second search reads the ring where the hand-over of the first puts it (chain_hand_over,
+    frame_end_pos) -- its expected input is the case buffer rotated by that amount; behind a failed search the slot stays empty"""
+    SC = sync_cases()
+    cases = SC.TWO_FRAME_CASES
+    iq = np.stack([c.iq for c in cases]); n = len(cases)
+    zero = np.zeros(n, np.int32)
+    for m in SC.METHODS:
+        outcomes = set()
+        d = d_factory(n_ensembles=n, max_frames=2, fft_placement=m, want_constellation=False)
+        try:
+            desc, cir, st = sync_run(d, SYNC_KERNELS["chain"], iq, zero, zero, zero + 5, n_frames=2)     # ratio 5: the gate stays closed, the frequency 0
+        finally:
+            d.close()
+        for i, c in enumerate(cases):
+            name = "%s, placement %d, chain" % (c.name, m)
+            i0, ir0 = R.orc_find_index(c.iq[:2048], m)
+            sync_assert_search(name + ", frame 0", desc[i, 0], cir[i, 0], i0, ir0)
+            if i0 < 0:
+                assert (int(desc[i, 1]["valid"]), int(desc[i, 1]["start_index"]), int(desc[i, 1]["pos"])) == (0, -1, 0) and not cir[i, 1].any(), (name, desc[i, 1])
+                outcomes.add("empty")
+                continue
+            i1, ir1 = R.orc_find_index(SC.second_frame_window(c, i0), m)
+            sync_assert_search(name + ", frame 1", desc[i, 1], cir[i, 1], i1, ir1, pos=i0 + SC.FRAME_ADVANCE)
+            outcomes.add("found" if i1 >= 0 else "failed")
+            assert all(int(desc[i, f][k]) == 0 for f in (0, 1) for k in ("coarse_ran", "coarse_after", "coarse_step")), (name, desc[i])
+        sync_assert_state(SYNC_KERNELS["chain"], st, [False] * n, [c.name for c in cases])
+        assert outcomes == {"empty", "found", "failed"}, (m, outcomes)
+
+
+def check_sync_find_errors(d_factory):
+    """wrong arguments: DABPHY_ERR_INVALID and no launch; afterwards the entry still works, and after dabphy_reset so does the receiver"""
+    from welle_io_amd.capi import DabPhyError
+    SC = sync_cases()
+    c = SC.WINDOW_CASES[[w.name for w in SC.WINDOW_CASES].index("tap@504")]
+    d = d_factory(n_ensembles=2, max_frames=2, fft_placement=0, want_constellation=False)
+    try:
+        x = synth.make_stream(4, snr_db=20, cfo_hz=30, delay=200, seed=4)
+        def two_frames():
+            d.stream_upload(np.tile(np.asarray(x, np.complex64), (2, 1)))
+            d.process(2)
+            return d.frame_info().copy(), [a.copy() for a in d.fibs()]
+        before = two_frames()
+        assert (before[0]["valid"] == 1).all()
+        iq = np.stack([c.iq, c.iq]); z = np.zeros(2, np.int32)
+        def invalid(fn):
+            try:
+                fn()
+            except DabPhyError as e:
+                assert "status -2" in str(e), str(e)                        # DABPHY_ERR_INVALID
+                return
+            raise AssertionError("expected DABPHY_ERR_INVALID")
+        invalid(lambda: d.test_sync_find(0, iq[:1], z[:1], z[:1], z[:1]))        # another ensemble count than the handle's
+        invalid(lambda: d.test_sync_find(0, np.stack([c.iq] * 3), np.zeros(3, np.int32), np.zeros(3, np.int32), np.zeros(3, np.int32)))
+        invalid(lambda: d.test_sync_find(3, iq, z, z, z))                         # unknown kernels
+        invalid(lambda: d.test_sync_find(-1, iq, z, z, z))
+        invalid(lambda: d.test_sync_find(2, iq, z, z, z, n_frames=3))             # more frames than max_frames
+        invalid(lambda: d.test_sync_find(2, iq, z, z, z, n_frames=0))
+        invalid(lambda: d.test_sync_find(0, iq, z, z, z, n_frames=2))             # only the find chain walks several frames
+        invalid(lambda: d.test_sync_find(1, iq, z, z, z, n_frames=2))
+        import ctypes as C
+        out = np.zeros((2, 1), d.test_sync_find(0, iq, z, z, z)[0].dtype); cir = np.zeros((2, 1, 2048), np.float32); st = np.zeros(2, [("pos", "<i8"), ("synced", "<i4"), ("lost", "<i4")])
+        ptr = [a.ctypes.data_as(C.c_void_p) for a in (iq, z, z, z, out, cir, st)]
+        for null in range(len(ptr)):                                              # a null pointer, in every position
+            a = [None if k == null else q for k, q in enumerate(ptr)]
+            invalid(lambda: d._chk(d.lib.dabphy_test_sync_find(d.h, 0, a[0], a[1], a[2], a[3], C.c_uint32(2), C.c_uint32(1), a[4], a[5], a[6])))
+        assert d.lib.dabphy_test_sync_find(None, 0, *ptr[:4], C.c_uint32(2), C.c_uint32(1), *ptr[4:]) == -2              # ... and no handle
+        for kernel in (0, 1, 2):
+            desc, _, state = d.test_sync_find(kernel, iq, z, z, z + 10)
+            assert (desc["start_index"] == 504).all() and (desc["valid"] == 2).all() and (state["synced"] == 1).all(), (kernel, desc)
+        d.reset()
+        after = two_frames()
+        assert before[0].tobytes() == after[0].tobytes() and all(np.array_equal(a, b) for a, b in zip(before[1], after[1]))      # (bytes: the SNR of a frame without a report is NaN)
+    finally:
+        d.close()
+
+
 def capi_tii_itemsize():
     return R.TII_EVENT_DTYPE.itemsize

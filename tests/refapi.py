@@ -128,6 +128,20 @@ def ref_find_index(v, method=2):
     return r, ir
 
 
+REF_PRS_SO = os.path.join(ROOT, "oracle", "_ref", "libwelle_ref_prs.so")
+_ref_prs = None
+
+
+def ref_coarse_prs(v, method):
+    """the reference's own OFDMProcessor::processPRS(v, FreqsyncMethod) (0 GetMiddle, 1 CorrelatePRS, 2 PatternOfZeros) -> carriers
+    (oracle/ref_prs_harness.cpp: a library of its own beside the harness library)"""
+    global _ref_prs
+    if _ref_prs is None:
+        _ref_prs = C.CDLL(REF_PRS_SO)
+    v = np.ascontiguousarray(v, np.complex64); assert len(v) == 2048
+    return _ref_prs.ref_coarse_prs(_p(v), int(method))
+
+
 def ref_freq_perm():
     a = np.zeros(1536, np.int16); ref().ref_freq_perm(_p(a)); return a
 
@@ -286,6 +300,19 @@ def orc_find_index(v, method=2):
 
 def orc_coarse_prs(v):
     v = np.ascontiguousarray(v, np.complex64); return orc().orc_coarse_prs(_p(v))
+
+
+def orc_std_sort_desc(value, index):
+    """the order std::sort leaves EarliestPeakWithBinning's bin peaks in (oracle/sort_order.cpp): bin numbers, highest peak first"""
+    value = np.ascontiguousarray(value, np.float32); index = np.ascontiguousarray(index, np.int32); order = np.zeros(len(value), np.int32)
+    orc().orc_std_sort_desc(_p(value), _p(index), len(value), _p(order))
+    return order
+
+
+def orc_coarse_prs_method(v, method):
+    """OFDMProcessor::processPRS restated: method = FreqsyncMethod (0 GetMiddle, 1 CorrelatePRS, 2 PatternOfZeros) -> carriers"""
+    v = np.ascontiguousarray(v, np.complex64); assert len(v) == 2048
+    return orc().orc_coarse_prs_method(_p(v), int(method))
 
 
 def orc_viterbi(soft, nbits):

@@ -346,3 +346,43 @@ def test_receiver_short_form_subchannels(oracle_built):
         assert m >= 8 * sc.frame_bytes, (i, len(a["msc"][i]), len(b["msc"][i]))
         assert a["msc"][i][:m] == b["msc"][i][:m], "sub-channel %d (%d kbit/s)" % (sc.subch_id, sc.bitrate)
         assert a["msc"][i][:m] in b"".join(tx.payload_log[sc.subch_id])
+
+
+@pytest.mark.parametrize("method", [0, 1, 2])
+def test_find_index_on_the_directed_window_cases(oracle_built, method):
+    """PhaseReference::findIndex itself on every window case of tests/sync_cases.py -- the inputs the kernels are checked on
+    (tests/test_emu_sync.py, tests/test_gpu_sync.py): the restatement's index and impulse response equal the reference's, bit for bit.
+    The binned method (1) sorts its bin peaks with std::sort, which leaves equal elements in an order of its own: the restatement asks
+    the same std::sort (oracle/sort_order.cpp), so inputs with bit-identical peaks are compared like any other.  On the three inputs whose
+    response is zero EVERYWHERE all 102 bins are equal, and the index is compared only in that both say -1."""
+    import sync_cases as SC
+    all_equal = {"zeros", "constant", "alternating"}
+    for c, (oi, oir) in zip(SC.WINDOW_CASES, SC.ORACLE_WINDOW[method]):
+        ri, rir = R.ref_find_index(c.iq[:2048], method)
+        assert np.array_equal(rir.view(np.uint32), oir.view(np.uint32)), (c.name, method)
+        if method == 1 and c.name in all_equal:
+            assert not rir.any() and (ri == -1) == (oi == -1), (c.name, ri, oi)
+        else:
+            assert ri == oi, (c.name, method, ri, oi)
+    for c in SC.TWO_FRAME_CASES:
+        i0, _ = R.orc_find_index(c.iq[:2048], method)
+        if i0 >= 0:
+            w = SC.second_frame_window(c, i0)
+            (ri, rir), (oi, oir) = R.ref_find_index(w, method), R.orc_find_index(w, method)
+            assert ri == oi and np.array_equal(rir.view(np.uint32), oir.view(np.uint32)), (c.name, method, ri, oi)
+
+
+@pytest.mark.parametrize("freqsync", [0, 1, 2])
+def test_process_prs_on_the_directed_coarse_cases(oracle_built, freqsync):
+    """OFDMProcessor::processPRS itself (GetMiddle, CorrelatePRS, PatternOfZeros) on the 2048 samples the coarse corrector reads in every
+    coarse case of tests/sync_cases.py, and on the window cases' windows for good measure: the restatement returns the same carrier count"""
+    import sync_cases as SC
+    for c, (s, _, _) in zip(SC.COARSE_CASES, SC.ORACLE_COARSE[freqsync]):
+        v = c.iq[s:s + 2048]
+        assert R.ref_coarse_prs(v, freqsync) == R.orc_coarse_prs_method(v, freqsync), (c.name, freqsync)
+    for c in SC.WINDOW_CASES:
+        assert R.ref_coarse_prs(c.iq[:2048], freqsync) == R.orc_coarse_prs_method(c.iq[:2048], freqsync), (c.name, freqsync)
+    for m in SC.METHODS:                                       # the receiver-layout cases, where each placement method takes the window
+        for c, (s, _, _) in zip(SC.RECEIVER_CASES, SC.ORACLE_RECEIVER[m][freqsync]):
+            ri, _ = R.ref_find_index(c.iq[:2048], m)
+            assert ri == s and R.ref_coarse_prs(c.iq[s:s + 2048], freqsync) == R.orc_coarse_prs_method(c.iq[s:s + 2048], freqsync), (c.name, m, freqsync)

@@ -40,6 +40,10 @@ MP2_EVENT_DTYPE = np.dtype([("frame", "<i4"), ("header", "<u4"), ("offset", "<i8
                             ("fpad", "u1", 2), ("pad_", "u1", 3)])      # dabphy_mp2_event
 AUDIO_DABPLUS, AUDIO_MP2 = 0, 1                                           # dabphy_set_audio_kinds_ensemble
 MSC_DESC_DTYPE = np.dtype([("ensemble", "<u4"), ("subch_index", "<u4"), ("row_bytes", "<u4"), ("first_valid", "<i4"), ("n_rows", "<i4"), ("subch_id", "<u4"), ("offset", "<u8")])
+SYNC_SERIAL, SYNC_WIDE, SYNC_CHAIN = 0, 1, 2                                # dabphy_test_sync_find: k_sync_find, k_sync_find_wide, k_sync_find_chain
+SYNC_CASE = 4096                                                            # DABPHY_TEST_SYNC_CASE
+SYNC_DESC_DTYPE = np.dtype([("pos", "<i8"), ("start_index", "<i4"), ("valid", "<i4"), ("coarse_ran", "<i4"), ("coarse_after", "<i4"), ("coarse_step", "<i4"), ("L1", "<i4")])   # dabphy_test_sync_desc
+SYNC_STATE_DTYPE = np.dtype([("pos", "<i8"), ("synced", "<i4"), ("lost", "<i4")])                                                  # dabphy_test_sync_state
 AU_OFF, AU_RAW, AU_LOAS = 0, 1, 2                                           # dabphy_set_au_drain
 AU_SERVICE_DTYPE = np.dtype([("ensemble", "<u4"), ("subch_index", "<u4"), ("subch_id", "<u4"), ("n_superframes", "<i4"), ("n_aus", "<i4"), ("n_failed", "<i4"),
                              ("first_au", "<u4"), ("pad_", "<u4"), ("offset", "<u8"), ("bytes", "<u8")])      # dabphy_au_service
@@ -238,6 +242,23 @@ class DabPhy:
         prs = np.ascontiguousarray(prs, np.complex64).reshape(B, F, 2048)
         valid = np.ones((B, F), np.int32) if valid is None else np.ascontiguousarray(valid, np.int32).reshape(B, F)
         self._chk(self.lib.dabphy_test_tii_pairs(self.h, _p(null), _p(prs), _p(valid), B, F))
+
+    def test_sync_find(self, kernel, iq, coarse, fine, fic_ratio, n_frames=1):
+        """dabphy_test_sync_find: one window-search launch (SYNC_SERIAL / SYNC_WIDE / SYNC_CHAIN) over the cases iq [B][4096], one per
+        ensemble, each with its starting correctors and FIC ratio -> (descriptors [B][n_frames] of SYNC_DESC_DTYPE, impulse responses
+        [B][n_frames][2048], receiver state [B] of SYNC_STATE_DTYPE).  The handle needs reset() before anything else"""
+        B = self.cfg.n_ensembles
+        iq = np.ascontiguousarray(iq, np.complex64).reshape(-1, SYNC_CASE)
+        coarse = np.ascontiguousarray(coarse, np.int32).reshape(-1); fine = np.ascontiguousarray(fine, np.int32).reshape(-1)
+        fic_ratio = np.ascontiguousarray(fic_ratio, np.int32).reshape(-1)
+        n = iq.shape[0]
+        if not (len(coarse) == len(fine) == len(fic_ratio) == n):
+            raise DabPhyError("test_sync_find: %d cases, %d / %d / %d parameters" % (n, len(coarse), len(fine), len(fic_ratio)))
+        F = max(int(n_frames), 1)
+        desc = np.zeros((n, F), SYNC_DESC_DTYPE); cir = np.zeros((n, F, 2048), np.float32); st = np.zeros(n, SYNC_STATE_DTYPE)
+        self._chk(self.lib.dabphy_test_sync_find(self.h, C.c_int32(int(kernel)), _p(iq), _p(coarse), _p(fine), _p(fic_ratio), C.c_uint32(n), C.c_uint32(int(n_frames)),
+                                                 _p(desc), _p(cir), _p(st)))
+        return desc, cir, st
 
     def test_tii_dropped(self):
         """dabphy_test_tii_dropped: measurements per ensemble that found all 32 slots taken"""

@@ -508,6 +508,69 @@ int dabphy_test_tii_pairs(dabphy_handle* h, const float* null, const float* prs,
     return sync(h);
 }
 
+// include/dabphy_test.h: ONE of the window-search launches dabphy_process queues (launch_sync_find, or the wide pass's k_sync_find_wide /
+// k_sync_find_chain alone) over a short looping ring per ensemble that holds the caller's case at position 0
+int dabphy_test_sync_find(dabphy_handle* h, int32_t kernel, const float* iq, const int32_t* coarse, const int32_t* fine, const int32_t* fic_ratio,
+                          uint32_t n_ens, uint32_t n_frames, dabphy_test_sync_desc* out, float* cir, dabphy_test_sync_state* state)
+{
+    DeviceBind dev_(h);
+    if (!h || !iq || !coarse || !fine || !fic_ratio || !out || !cir || !state || n_ens != h->cfg.n_ensembles || n_frames == 0 || n_frames > h->cfg.max_frames) return DABPHY_ERR_INVALID;
+    if (kernel < DABPHY_TEST_SYNC_SERIAL || kernel > DABPHY_TEST_SYNC_CHAIN || (kernel != DABPHY_TEST_SYNC_CHAIN && n_frames != 1)) return DABPHY_ERR_INVALID;
+    const uint32_t B = n_ens, F = n_frames;
+    constexpr int64_t CASE = DABPHY_TEST_SYNC_CASE, RING = 2 * CASE;      // the case, then as many zeros: a search at the last sample of the case still reads inside the ring
+    int r;
+    // a synchroniser that runs ahead of the decoder (pipelined schedules) shares the state blocks: it ends first
+    if (h->s_desc2[0].p && (r = resolve_all_chains(h))) return r;
+    if (h->sync_stream) HIPCHK(h, hipStreamSynchronize(h->sync_stream));
+    std::vector<cf32> ring((size_t)B * RING);                             // (zeros behind the case)
+    std::vector<RxState> st(B);
+    std::vector<DecState> dec(B);
+    for (uint32_t b = 0; b < B; b++) {
+        memcpy(ring.data() + (size_t)b * RING, iq + 2 * (size_t)b * CASE, CASE * sizeof(cf32));
+        RxState& s = st[b];
+        memset(&s, 0, sizeof s);                                          // pos = 0, local_phase = 0: with coarse + fine = 0 the oscillator stays at 1 + 0j
+        s.synced = 1; s.coarse = coarse[b]; s.fine = fine[b]; s.first_lock_attempts = -1; s.acq_phase = 1;
+        s.calm_frames = 1 << 20;                                          // a receiver long in lock: the wide pass takes it
+        memset(&dec[b], 0, sizeof dec[b]);
+        dec[b].fic_ratio = fic_ratio[b]; dec[b].first_stale_frame = -1; dec[b].first_effective_frame = -1;
+    }
+    if ((r = ensure(h, h->iq, ring.size() * sizeof(cf32)))) return r;
+    if ((r = ensure(h, h->desc, (size_t)B * F * sizeof(FrameDesc)))) return r;
+    if ((r = ensure(h, h->prs_mag, (size_t)B * F * T_U * sizeof(float)))) return r;
+    if ((r = ensure(h, h->s_hist, (size_t)B * HIST_CAP * sizeof(FrameDesc)))) return r;
+    if ((r = ensure(h, h->s_redo[0], (size_t)B * sizeof(int32_t)))) return r;
+    HIPCHK(h, hipMemcpyAsync(h->iq.p, ring.data(), ring.size() * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_state, st.data(), st.size() * sizeof(RxState), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_dec, dec.data(), dec.size() * sizeof(DecState), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->desc.p, 0, (size_t)B * F * sizeof(FrameDesc), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->prs_mag.p, 0, (size_t)B * F * T_U * sizeof(float), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->s_redo[0].p, 0, (size_t)B * sizeof(int32_t), h->stream));      // the find chain starts at frame redo_out[b] = 0
+    // the argument block of sync_args (dabphy_stream.hip), on this entry's ring and descriptors instead of the bound stream's
+    SyncArgs sa{};
+    sa.tab = h->tab; sa.iq = h->iq.as<cf32>(); sa.iq_stride = (size_t)RING; sa.ring = RING; sa.n_valid = RING; sa.loop = 1;
+    sa.state = h->d_state; sa.dec = h->d_dec; sa.desc = h->desc.as<FrameDesc>(); sa.n_ens = (int)B; sa.n_frames = (int)F; sa.frame = 0;
+    sa.fft_placement = h->cfg.fft_placement; sa.disable_coarse = h->cfg.disable_coarse; sa.freqsync = h->cfg.freqsync_method;
+    sa.cir = h->prs_mag.as<float>();
+    sa.hist = h->s_hist.as<FrameDesc>(); sa.hist_cap = HIST_CAP; sa.level_max = 3.0e38f;
+    if (kernel == DABPHY_TEST_SYNC_SERIAL) launch_sync_find(sa, h->stream);
+    else {
+        sa.redo_out = h->s_redo[0].as<int32_t>(); sa.any_redo = h->d_any_redo; sa.any_chain = h->d_any_redo + dabphy_handle::N_DESC;
+        if (kernel == DABPHY_TEST_SYNC_WIDE) launch_sync_find_wide(sa, h->stream); else launch_sync_find_chain(sa, h->stream);
+    }
+    std::vector<FrameDesc> d((size_t)B * F);
+    HIPCHK(h, hipMemcpyAsync(d.data(), h->desc.p, d.size() * sizeof(FrameDesc), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(st.data(), h->d_state, st.size() * sizeof(RxState), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(cir, h->prs_mag.p, (size_t)B * F * T_U * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if ((r = sync(h))) return r;
+    for (size_t i = 0; i < d.size(); i++) {
+        dabphy_test_sync_desc& o = out[i];
+        o.pos = d[i].pos; o.start_index = d[i].start_index; o.valid = d[i].valid; o.coarse_ran = d[i].coarse_ran;
+        o.coarse_after = d[i].coarse_after; o.coarse_step = d[i].coarse_step; o.L1 = d[i].L1;
+    }
+    for (uint32_t b = 0; b < B; b++) { state[b].pos = st[b].pos; state[b].synced = st[b].synced; state[b].lost = st[b].lost; }
+    return DABPHY_OK;
+}
+
 int dabphy_test_tii_dropped(dabphy_handle* h, int32_t* per_ensemble)
 {
     DeviceBind dev_(h);

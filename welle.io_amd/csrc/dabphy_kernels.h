@@ -377,6 +377,8 @@ void dump_chain_ts();
 void launch_sync_find(const SyncArgs& a, hipStream_t s);
 void launch_sync_wide(const SyncArgs& a, hipStream_t s, hipEvent_t front = nullptr);      // front: recorded behind the wide pass proper (searches, sums, judge), in front of the find chain's rounds
 void launch_sync_finish(const SyncArgs& a, hipStream_t s);
+void launch_sync_find_wide(const SyncArgs& a, hipStream_t s);                              // k_sync_find_wide alone: grid (n_frames, n_ens)
+void launch_sync_find_chain(const SyncArgs& a, hipStream_t s);                             // k_sync_find_chain alone: from a.redo_out[b] on
 void launch_slevel_catchup(const SyncArgs& a, hipStream_t s);
 
 } // namespace dabphy

@@ -840,6 +840,15 @@ void launch_slevel_catchup(const SyncArgs& a, hipStream_t s)
     hipLaunchKernelGGL(k_slevel_catchup, dim3(a.n_ens), dim3(256), 0, s, a);
 }
 
+// the two window-search launches of the wide pass, each stated once (launch_sync_wide below; dabphy_test_sync_find runs either alone)
+void launch_sync_find_wide(const SyncArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sync_find_wide, dim3(a.n_frames, a.n_ens), dim3(FFT_THREADS), 0, s, a);
+}
+void launch_sync_find_chain(const SyncArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sync_find_chain, dim3(a.n_ens), dim3(FFT_THREADS), 0, s, a);
+}
 void launch_sync_wide(const SyncArgs& a, hipStream_t s, hipEvent_t front)
 {
     if (a.skip_wide) {
@@ -848,7 +857,7 @@ void launch_sync_wide(const SyncArgs& a, hipStream_t s, hipEvent_t front)
         // profiles/r06_drift_kernel_stats.csv) -- so the pass starts in the find chain for everybody
         hipError_t e = hipMemsetAsync(a.redo_out, 0, sizeof(int32_t) * (size_t)a.n_ens, s); (void)e;
     } else {
-        hipLaunchKernelGGL(k_sync_find_wide, dim3(a.n_frames, a.n_ens), dim3(FFT_THREADS), 0, s, a);
+        launch_sync_find_wide(a, s);
         hipLaunchKernelGGL(k_sync_finish_wide, dim3(a.n_frames, a.n_ens), dim3(FINISH_THREADS), 0, s, a);
         hipLaunchKernelGGL(k_sync_validate, dim3((a.n_ens + 63) / 64), dim3(64), 0, s, a);
     }
@@ -859,7 +868,7 @@ void launch_sync_wide(const SyncArgs& a, hipStream_t s, hipEvent_t front)
     SyncArgs c = a;
     for (int r = 0; r < SYNC_CHAIN_ROUNDS; r++) {
         c.last_round = r == SYNC_CHAIN_ROUNDS - 1;
-        hipLaunchKernelGGL(k_sync_find_chain, dim3(c.n_ens), dim3(FFT_THREADS), 0, s, c);
+        launch_sync_find_chain(c, s);
         hipLaunchKernelGGL(k_sync_finish_wide, dim3(c.n_frames, c.n_ens), dim3(FINISH_THREADS), 0, s, c);
         hipLaunchKernelGGL(k_sync_validate_chain, dim3((c.n_ens + 63) / 64), dim3(64), 0, s, c);
     }

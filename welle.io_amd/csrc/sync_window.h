@@ -63,41 +63,133 @@ __device__ __forceinline__ int window_strongest_peak(const float* lbuf, float* r
     return first;
 }
 
+// ---- the order std::sort leaves the bin peaks in (phasereference.cpp:172-175: descending by value).  Among bit-identical peaks -- equal
+// echoes give them -- it is whatever the C++ library's sort does, and which of them land among the first four decides the window index:
+// this is that sort as libstdc++ runs it (introsort: median-of-three partitions down to 16 elements, heap sort below the depth limit,
+// one insertion pass at the end), comparison for comparison, on bin numbers.  One thread; ord: the n bin numbers in ascending order on
+// entry; stk: 3 ints per pending partition (at most 2 lg n + 1 of them).  The equal-echo families of tests/sync_cases.py need it; the
+// restatement it is checked against calls std::sort itself (oracle/sort_order.cpp).  Out of line on purpose: it runs for tied peaks only, and
+// inlined it changed how the compiler lays out the window search around it (measured 0.2 % on the headline; out of line: level).
+__device__ __attribute__((noinline)) void std_sort_bins_desc(const float* val, int* ord, int* stk, const int n)
+{
+    const auto before = [&](int a, int b) { return val[a] > val[b]; };          // comp(lhs, rhs) on bin numbers
+    const auto swp = [&](int i, int j) { const int x = ord[i]; ord[i] = ord[j]; ord[j] = x; };
+    // std::__adjust_heap and the __push_heap at its end
+    const auto adjust_heap = [&](int first, int hole, int len, int value) {
+        const int top = hole;
+        int child = hole;
+        while (child < (len - 1) / 2) {
+            child = 2 * (child + 1);
+            if (before(ord[first + child], ord[first + child - 1])) child--;
+            ord[first + hole] = ord[first + child]; hole = child;
+        }
+        if ((len & 1) == 0 && child == (len - 2) / 2) { child = 2 * (child + 1); ord[first + hole] = ord[first + child - 1]; hole = child - 1; }
+        int parent = (hole - 1) / 2;
+        while (hole > top && before(ord[first + parent], value)) { ord[first + hole] = ord[first + parent]; hole = parent; parent = (hole - 1) / 2; }
+        ord[first + hole] = value;
+    };
+    const auto unguarded_linear_insert = [&](int last) {
+        const int value = ord[last];
+        int next = last - 1;
+        while (before(value, ord[next])) { ord[last] = ord[next]; last = next; next--; }
+        ord[last] = value;
+    };
+    // std::__introsort_loop, its recursion on the upper part kept on a stack
+    int sp = 0;
+    stk[0] = 0; stk[1] = n; stk[2] = 2 * (31 - __builtin_clz((unsigned)n)); sp = 1;
+    while (sp > 0) {
+        sp--;
+        const int first = stk[3 * sp];
+        int last = stk[3 * sp + 1], depth = stk[3 * sp + 2];
+        while (last - first > 16) {
+            if (depth == 0) {                                                     // std::__partial_sort(first, last, last): make_heap, sort_heap
+                const int len = last - first;
+                for (int parent = (len - 2) / 2; parent >= 0; parent--) adjust_heap(first, parent, len, ord[first + parent]);
+                while (last - first > 1) { last--; const int value = ord[last]; ord[last] = ord[first]; adjust_heap(first, 0, last - first, value); }
+                break;
+            }
+            depth--;
+            const int a = first + 1, b = first + (last - first) / 2, c = last - 1;      // std::__move_median_to_first
+            if (before(ord[a], ord[b])) {
+                if (before(ord[b], ord[c])) swp(first, b); else if (before(ord[a], ord[c])) swp(first, c); else swp(first, a);
+            } else if (before(ord[a], ord[c])) swp(first, a);
+            else if (before(ord[b], ord[c])) swp(first, c);
+            else swp(first, b);
+            int lo = first + 1, hi = last;                                        // std::__unguarded_partition around ord[first]
+            for (;;) {
+                while (before(ord[lo], ord[first])) lo++;
+                hi--;
+                while (before(ord[first], ord[hi])) hi--;
+                if (!(lo < hi)) break;
+                swp(lo, hi); lo++;
+            }
+            stk[3 * sp] = lo; stk[3 * sp + 1] = last; stk[3 * sp + 2] = depth; sp++;
+            last = lo;
+        }
+    }
+    // std::__final_insertion_sort
+    const int head = n > 16 ? 16 : n;
+    for (int i = 1; i < head; i++) {
+        if (before(ord[i], ord[0])) { const int value = ord[i]; for (int j = i; j > 0; j--) ord[j] = ord[j - 1]; ord[0] = value; }
+        else unguarded_linear_insert(i);
+    }
+    for (int i = head; i < n; i++) unguarded_linear_insert(i);
+}
+
 // ---- FFTPlacementMethod::EarliestPeakWithBinning (phasereference.cpp:125-211): peaks over 102 bins of 20 samples (2040..2047 are
 // never looked at), the highest peak, the 4 highest bins within 500 samples of it, those above 3 * mean, the earliest.
-// pa: T_U floats of LDS behind lbuf (bin peaks and their indices).
+// pa: T_U floats of LDS behind lbuf (bin peaks and their indices; the sort's permutation and stack when it is needed).
 __device__ __forceinline__ int window_earliest_peak_binned(const float* lbuf, float* pa, int* redi, float* s_sum, float* cir, const int t)
 {
+    constexpr int NB = 102;
     float* const bval = pa; int* const bidx = reinterpret_cast<int*>(pa + 128);
+    int* const ord = reinterpret_cast<int*>(pa + 256); int* const stk = reinterpret_cast<int*>(pa + 384);
     if (t == 0) { float s = 0; for (int i = 0; i < 2040; i++) s += lbuf[i]; *s_sum = s; }    // `mean += value` in index order
-    if (t < 102) {
+    if (t < NB) {
         float pv = 0.0f; int pi = -1;
         for (int j = 0; j < 20; j++) { const float v2 = lbuf[20 * t + j]; if (v2 > pv) { pv = v2; pi = 20 * t + j; } }
-        bval[t] = pv; bidx[t] = pi;
+        bval[t] = pv; bidx[t] = pi; ord[t] = t;
     }
     if (cir && t < 8) cir[2040 + t] = 0.0f;                                                  // the reference's buffer keeps its zeros there
     __syncthreads();
     if (t == 0) {
         const float mean = *s_sum / T_U;
-        // std::sort by value (descending) is replaced by selection: the order among exactly equal peaks is the bin order
-        int top = 0;
-        for (int k = 1; k < 102; k++) if (bval[k] > bval[top]) top = k;
+        // std::sort by value (descending) is replaced by selection -- as long as no two peaks that matter are bit-identical: the highest
+        // one (the distances are taken from it), and the fourth against the fifth of those within 500 samples (the first four are kept).
+        // `ties` counts the bins that equal the one selected and were passed over, in those two places.
+        int top = 0, ties = 0, ties4 = 0;
+        for (int k = 1; k < NB; k++) { if (bval[k] > bval[top]) { top = k; ties = 0; } else if (bval[k] == bval[top]) ties++; }
         const int peak_index = bidx[top];
         unsigned long long used_lo = 0, used_hi = 0;
         int found = 0, mn = 0;
-        for (int pass = 0; pass < 4; pass++) {
+        for (int pass = 0; pass < 4 && bval[top] != 0.0f; pass++) {
             int best = -1;
-            for (int k = 0; k < 102; k++) {
+            for (int k = 0; k < NB; k++) {
                 const bool used = k < 64 ? (used_lo >> k) & 1 : (used_hi >> (k - 64)) & 1;
                 const int dist = bidx[k] - peak_index;
                 if (used || (dist < 0 ? -dist : dist) > 500) continue;
-                if (best < 0 || bval[k] > bval[best]) best = k;
+                if (best < 0 || bval[k] > bval[best]) { best = k; ties4 = 0; }
+                else if (pass == 3 && bval[k] == bval[best]) ties4++;
             }
             if (best < 0) break;
             if (best < 64) used_lo |= 1ull << best; else used_hi |= 1ull << (best - 64);
             if (bval[best] < 3 * mean) continue;
             if (!found || bidx[best] < mn) { mn = bidx[best]; found = 1; }
         }
+        if ((ties | ties4) != 0 && bval[top] != 0.0f) {
+            // bit-identical peaks where it matters: the library's order decides (std_sort_bins_desc), then phasereference.cpp:177-209 as written
+            std_sort_bins_desc(bval, ord, stk, NB);
+            const int peak2 = bidx[ord[0]];
+            found = 0; mn = 0;
+            for (int a = 0, kept = 0; a < NB && kept < 4; a++) {
+                const int k = ord[a], dist = bidx[k] - peak2;
+                if ((dist < 0 ? -dist : dist) > 500) continue;
+                kept++;
+                if (bval[k] < 3 * mean) continue;
+                if (!found || bidx[k] < mn) { mn = bidx[k]; found = 1; }
+            }
+        }
+        // (an all-zero response: every bin holds index -1 and passes `0 < 3 * 0`: min_element gives -1, which is also "no peak")
         redi[0] = found ? mn : -1;
     }
     __syncthreads();
