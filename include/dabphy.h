@@ -59,7 +59,8 @@ typedef enum {
 uint32_t dabphy_abi_version(void);
 typedef enum { DABPHY_STRUCT_CONFIG = 0, DABPHY_STRUCT_FRAME_INFO = 1, DABPHY_STRUCT_SF_EVENT = 2, DABPHY_STRUCT_SUBCHANNEL = 3,
                DABPHY_STRUCT_PROTECTION = 4, DABPHY_STRUCT_TII_MEASUREMENT = 5, DABPHY_STRUCT_MSC_DESC = 6,
-               DABPHY_STRUCT_MP2_EVENT = 7, DABPHY_STRUCT_AU_SERVICE = 8, DABPHY_STRUCT_AU_DESC = 9 } dabphy_struct_id;
+               DABPHY_STRUCT_MP2_EVENT = 7, DABPHY_STRUCT_AU_SERVICE = 8, DABPHY_STRUCT_AU_DESC = 9,
+               DABPHY_STRUCT_WIDEBAND_CONFIG = 10 } dabphy_struct_id;
 size_t dabphy_struct_size(int32_t which);      /* 0 for an unknown id */
 
 /* RadioReceiverOptions (src/backend/radio-receiver-options.h:66-84) + batch geometry */
@@ -225,6 +226,40 @@ int dabphy_stream_write_raw(dabphy_handle* h, const void* data, uint64_t n_sampl
  * alternate between two host buffers. */
 int dabphy_stream_write_raw_async(dabphy_handle* h, const void* data, uint64_t n_samples, int32_t format);
 int dabphy_stream_commit(dabphy_handle* h);
+
+/* Wideband front end: ONE capture that covers several DAB blocks, at decimation x 2.048 MS/s, channelised on the device into the ring
+ * rows of the handle's ensembles -- what a caller otherwise does on the CPU with one long FIR per block.  (The reference has no such
+ * stage: its front ends deliver 2.048 MS/s; input/airspy_sdr.cpp:187-202 averages pairs.)  With x[i] the capture's i-th complex sample
+ * since the open call (x[i] = 0 for i < 0), c() the conversion of `format` above, D = decimation and P = 128 D, ensemble e receives
+ *     y_e[m] = sum_{k = 0 .. n_taps - 1} taps[k] * c(x[m D + D - 1 - k]) * exp(-2 pi j ((offset_16khz[e] * (m D + D - 1 - k)) mod P) / P)
+ * as sample m of its ring row: mixed down by offset_16khz[e] x 16 kHz (the block's centre minus the capture's; every DAB block centre is a
+ * multiple of 16 kHz, so the oscillator repeats after P capture samples: a table made in double precision, indexed exactly, no drift),
+ * low-pass filtered with the caller's real taps and decimated.  Sums run in fp32; a capture written in any sequence of pieces gives the
+ * same bits as one written at once (the last n_taps - 1 samples and the capture index are carried from write to write).
+ *   dabphy_stream_open_wideband      dabphy_stream_open (reset included) + the tables; taps and offsets are copied.  Every buffer the
+ *                                    writes need is created here, staging for the largest write included.  DABPHY_ERR_INVALID: a null
+ *                                    pointer, struct_size not this library's, decimation outside 1 .. 32, n_taps outside 1 .. 1024,
+ *                                    |offset| > 64 D, an unknown format, ring_samples as for dabphy_stream_open.
+ *   dabphy_stream_write_wideband     n_capture_samples of the capture ([sample] interleaved I/Q in the configured format) -> n / D samples
+ *                                    behind those written so far, in every ensemble's row; as dabphy_stream_write_raw otherwise.
+ *                                    DABPHY_ERR_INVALID: a null pointer, n = 0, n not a multiple of D, n / D > ring_samples.
+ *   dabphy_stream_write_wideband_async   as dabphy_stream_write_raw_async: copy stream, two staging slots, the same lifetime rule for
+ *                                    `data`; visible after dabphy_stream_commit.  A synchronous write while uncommitted samples are
+ *                                    queued returns DABPHY_ERR_STATE (the carry follows the order of the calls).
+ * A wideband write on a stream opened otherwise, and dabphy_stream_write / _write_raw / _write_raw_async on a wideband stream, return
+ * DABPHY_ERR_STATE.  dabphy_reset clears the carry and the capture index and keeps the configuration; dabphy_stream_open,
+ * _bind_device and _upload drop it.  A FIR's output is not bounded by 1: the stream counts as unbounded, like a cf32 write. */
+typedef struct {
+    uint32_t struct_size;           /* sizeof(dabphy_wideband_config) as the CALLER was compiled; fields are only ever appended */
+    uint32_t decimation;            /* D: the capture's rate is D x 2.048 MS/s */
+    uint32_t n_taps;
+    const float* taps;              /* [n_taps] real low-pass at the capture's rate, tap 0 on the newest sample */
+    const int32_t* offset_16khz;    /* [n_ensembles] block centre minus capture centre, in units of 16 kHz */
+    int32_t format;                 /* dabphy_sample_format of the capture */
+} dabphy_wideband_config;
+int dabphy_stream_open_wideband(dabphy_handle* h, uint64_t ring_samples, const dabphy_wideband_config* cfg);
+int dabphy_stream_write_wideband(dabphy_handle* h, const void* data, uint64_t n_capture_samples);
+int dabphy_stream_write_wideband_async(dabphy_handle* h, const void* data, uint64_t n_capture_samples);
 
 /* diagnostics: n samples of ensemble `ensemble` starting at absolute sample index `pos`, as they lie in the ring (cf32), e.g. to
  * compare the device's format conversion with CRAWFile::convertSamples */

@@ -4,4 +4,5 @@ csrc/      hand-written HIP kernels for gfx950 + the C ABI (include/dabphy.h) ->
 host/      C++ mirror of the reference's backend interface for this path (RadioReceiver facade over the C ABI)
 capi.py    ctypes binding used by tests/ and bench.py
 synth.py   synthetic Mode-I transmit chain (test / bench input only)
+wideband.py  low-pass design and synthetic multi-block captures for the wideband front end (dabphy_stream_open_wideband)
 """

@@ -21,6 +21,16 @@ class Config(C.Structure):
                 ("want_impulse_response", C.c_int32), ("demod_chunk", C.c_int32), ("freqsync_method", C.c_int32), ("pipeline_sync", C.c_int32), ("serial_sync", C.c_int32), ("no_batch_replay", C.c_int32), ("decode_shape", C.c_int32), ("sync_early", C.c_int32)]
 
 
+class WidebandConfig(C.Structure):
+    """dabphy_wideband_config"""
+    _fields_ = [("struct_size", C.c_uint32), ("decimation", C.c_uint32), ("n_taps", C.c_uint32), ("taps", C.POINTER(C.c_float)),
+                ("offset_16khz", C.POINTER(C.c_int32)), ("format", C.c_int32)]
+
+
+FORMATS = {"cf32": 0, "u8": 1, "s8": 2, "s16le": 3, "s16be": 4}              # dabphy_sample_format
+FORMAT_BYTES = {0: 8, 1: 2, 2: 2, 3: 4, 4: 4}                                # per complex sample
+
+
 class Protection(C.Structure):
     _fields_ = [("nbits", C.c_int32), ("L", C.c_int32 * 4), ("PI", C.c_int32 * 4)]
 
@@ -515,6 +525,34 @@ class DabPhy:
         assert data.flags["C_CONTIGUOUS"]
         bps = 2 if code <= 2 else 4
         self._chk(self.lib.dabphy_stream_write_raw_async(self.h, _p(data), C.c_uint64(data.nbytes // (self.cfg.n_ensembles * bps)), code))
+
+    # ---- wideband front end: one capture at decimation x 2.048 MS/s, channelised on the device into every ensemble's ring row
+    def stream_open_wideband(self, ring_samples, decimation, taps, offsets, fmt):
+        """taps: real low-pass at the capture's rate (wideband.design_taps); offsets: per ensemble, block centre minus capture centre in
+        units of 16 kHz; fmt: "cf32", "u8", "s8", "s16le", "s16be" (dabphy_stream_open_wideband: stream_open + the tables)"""
+        taps = np.ascontiguousarray(taps, np.float32).reshape(-1); offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        if len(offsets) != self.cfg.n_ensembles:
+            raise DabPhyError("stream_open_wideband: %d offsets for %d ensembles" % (len(offsets), self.cfg.n_ensembles))
+        cfg = WidebandConfig(C.sizeof(WidebandConfig), int(decimation), len(taps), taps.ctypes.data_as(C.POINTER(C.c_float)),
+                             offsets.ctypes.data_as(C.POINTER(C.c_int32)), FORMATS[fmt])
+        self._chk(self.lib.dabphy_stream_open_wideband(self.h, C.c_uint64(ring_samples), C.byref(cfg)))
+        self._wb = (int(decimation), FORMAT_BYTES[FORMATS[fmt]])
+
+    def stream_write_wideband(self, data):
+        """data: the capture's next samples, [n][2] integers of the configured format (or complex64); n a multiple of the decimation"""
+        data = np.ascontiguousarray(data)
+        self._chk(self.lib.dabphy_stream_write_wideband(self.h, _p(data), C.c_uint64(data.nbytes // self._wb[1])))
+
+    def stream_write_wideband_async(self, data):
+        """the same on the copy stream (visible after stream_commit); `data` stays untouched until the next-but-one call returns"""
+        assert data.flags["C_CONTIGUOUS"]
+        self._chk(self.lib.dabphy_stream_write_wideband_async(self.h, _p(data), C.c_uint64(data.nbytes // self._wb[1])))
+
+    def time_wideband(self, warmup=3, iters=20):
+        """device milliseconds of `iters` repeats of the last stream_write_wideband's launches on its staged capture (dabphy_time_wideband)"""
+        ms = np.zeros(iters, np.float32)
+        self._chk(self.lib.dabphy_time_wideband(self.h, C.c_uint32(warmup), C.c_uint32(iters), _p(ms)))
+        return ms
 
     def stream_read(self, ensemble, pos, n):
         out = np.zeros(n, np.complex64)

@@ -19,6 +19,7 @@ size_t dabphy_struct_size(int32_t which)
         case DABPHY_STRUCT_MP2_EVENT: return sizeof(dabphy_mp2_event);
         case DABPHY_STRUCT_AU_SERVICE: return sizeof(dabphy_au_service);
         case DABPHY_STRUCT_AU_DESC: return sizeof(dabphy_au_desc);
+        case DABPHY_STRUCT_WIDEBAND_CONFIG: return sizeof(dabphy_wideband_config);
     }
     return 0;
 }

@@ -1,7 +1,7 @@
 // welle.io_amd/csrc/dabphy_internal.h -- what the translation units of the C ABI share: the handle (streams, events, device buffers of one
 // receiver batch), small host helpers, and the internal functions that cross files.  Not installed, not part of include/dabphy.h.
 //   dabphy_api.hip          create / destroy / options / sub-channel classes, the stateless seams (demod, Viterbi, FIC, RS) and the timing drivers
-//   dabphy_stream.hip       sample rings (bind / upload / write / raw formats), the synchroniser's chain and wide pass, reset
+//   dabphy_stream.hip       sample rings (bind / upload / write / raw formats / wideband capture), the synchroniser's chain and wide pass, reset
 //   dabphy_process.hip      dabphy_process: the pipelined schedules, exact batch mode (replay), the decode of one batch as named steps
 //   dabphy_fused.hip        the fused decode's host side: per-class step tables, the launch plan (build, classes, work list)
 //   dabphy_superframes.hip  Reed-Solomon seams and the DAB+ superframe filter
@@ -129,6 +129,17 @@ struct dabphy_handle {
     DevBuf s_raw2[2]; hipStream_t copy_stream = nullptr; hipEvent_t ev_ingest[2] = {nullptr, nullptr}; int raw_sel = 0;   // dabphy_stream_write_raw_async
     uint64_t s_enqueued = 0; int commit_slot = -1;    // samples handed to the copy stream so far; slot whose event covers the committed ones
     DevBuf s_null;                          // null symbols on request (dabphy_get_null_symbols)
+    // Wideband front end (dabphy_stream_open_wideband; k_wideband.hip): one capture at D x 2.048 MS/s channelised into the ring rows.  The
+    // open call creates every buffer -- tables, both carries, the three staging buffers at the largest write (ring * D samples) -- and
+    // a plain open or bind drops the configuration (the buffers stay with the handle, grow-only like the rest).  Carried from write to
+    // write: the carry (dabphy_reset clears it) and the absolute capture index `abs`; both follow the order the writes are QUEUED in.
+    struct Wideband {
+        bool on = false;
+        uint32_t D = 0, n_taps = 0, e_pad = 0; int32_t format = 0;
+        DevBuf ctaps, osc, om, carry[2]; int carry_sel = 0;      // carry[carry_sel] lies in front of the next write
+        uint64_t abs = 0;                                        // capture samples written since the open / reset
+        WidebandArgs last{}; bool last_valid = false;            // the last synchronous write as it was launched (dabphy_time_wideband runs it again)
+    } wb;
     // bulk MSC drain (dabphy_msc_drain_begin / _wait): the class outputs leave on a stream of their own while the next batch starts
     hipStream_t drain_stream = nullptr; hipEvent_t ev_drain_done = nullptr, ev_drain_staged = nullptr; bool drain_pending = false; DevBuf drain_stage;
     DevBuf sf_events, sf_count, sf_bytes, sf_stats, sf_gf, sf_accept; const FrameDesc* last_desc = nullptr;

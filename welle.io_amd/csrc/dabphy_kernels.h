@@ -280,6 +280,48 @@ struct IngestArgs {
     int format;                                           // dabphy_sample_format
 };
 void launch_ingest(const IngestArgs& a, int n_ens, hipStream_t s);
+// Sample i of a raw stream as cf32: the arithmetic of CRAWFile::convertSamples (k_ingest.hip's header has the formats), stated once for
+// k_ingest and the wideband channeliser.  format = DABPHY_FMT_U8 ... _S16BE
+__device__ __forceinline__ cf32 ingest_sample(const uint8_t* __restrict__ src, uint64_t i, int format)
+{
+    cf32 v;
+    if (format == 1) {                                    // U8
+        const uint16_t w = reinterpret_cast<const uint16_t*>(src)[i];
+        v.re = (float)((int)(w & 0xff) - 128) * 0.0078125f; v.im = (float)((int)(w >> 8) - 128) * 0.0078125f;
+    } else if (format == 2) {                             // S8
+        const uint16_t w = reinterpret_cast<const uint16_t*>(src)[i];
+        v.re = (float)(int8_t)(w & 0xff) * 0.0078125f; v.im = (float)(int8_t)(w >> 8) * 0.0078125f;
+    } else {                                              // S16 "LE" (3) / "BE" (4)
+        const uint32_t w = reinterpret_cast<const uint32_t*>(src)[i];
+        const uint32_t b0 = w & 0xff, b1 = (w >> 8) & 0xff, b2 = (w >> 16) & 0xff, b3 = w >> 24;
+        const int16_t I = format == 3 ? (int16_t)((b0 << 8) | b1) : (int16_t)((b1 << 8) | b0);
+        const int16_t Q = format == 3 ? (int16_t)((b2 << 8) | b3) : (int16_t)((b3 << 8) | b2);
+        v.re = (float)I; v.im = (float)Q;
+    }
+    return v;
+}
+
+// Wideband channeliser (k_wideband.hip): one capture at D x 2.048 MS/s -> the ring rows of the handle's ensembles.
+//   y_e[m] = osc[(om_e * a) mod P] * sum_k ctaps[k][e] * c(x[a - k]),   a = m D + D - 1 (absolute capture index), P = 128 D
+// with ctaps[k][e] = taps[k] exp(+2 pi j ((om_e k) mod P) / P) and osc[p] = exp(-2 pi j p / P), both made by the host in double precision
+// (dabphy_stream_open_wideband).  Every output sums k = 0 ... n_taps - 1 in that order, wherever it falls in a call or in a tile.
+constexpr int WB_MAX_D = 32, WB_MAX_TAPS = 1024, WB_ENS_STEP = 4;     // WB_ENS_STEP: ensembles one pass over a tile serves (ctaps rows are padded to it with zeros)
+constexpr int WB_OUT_STEP = 2;                                       // outputs per lane: one load of a tap serves both
+constexpr int WB_TAP_STEP = 4;                                       // taps the kernel adds per step, the next step's operands being fetched meanwhile
+constexpr int WB_TILE_SMALL = 2560, WB_TILE_MID = 4864, WB_TILE_LARGE = 7168;   // samples of LDS tile the kernel's three builds hold (8, 4, 2 work-groups per compute unit)
+// taps the kernel FETCHES for a filter of n_taps: whole steps, and one step ahead -- rows of the tap table (zeros from n_taps on) and samples of halo
+constexpr uint32_t wideband_reach(uint32_t n_taps) { return (n_taps + WB_TAP_STEP - 1) / WB_TAP_STEP * WB_TAP_STEP + WB_TAP_STEP; }
+struct WidebandArgs {
+    const uint8_t* raw; int format; uint64_t n, n_out;    // the call's capture: n samples (c() = ingest_sample, or cf32 as it is), n_out = n / D outputs
+    const cf32* carry_in; cf32* carry_out;                // the n_taps - 1 converted samples in front of the call / behind it (two buffers, swapped by the host)
+    const cf32* ctaps; const cf32* osc; const uint32_t* om;   // [wideband_reach(n_taps)][e_pad] (zeros from row n_taps on), [P], [n_ens] offset mod P
+    cf32* iq; size_t iq_stride; uint64_t ring, w;         // output 0 goes to ring position w of every row
+    uint32_t D, n_taps, P, n_ens, e_pad, abs_mod;         // abs_mod: absolute index of the call's first capture sample, mod P
+    uint32_t T, halo, W;                                  // outputs per tile (512, 256 or 128: the 256 threads are 512 / T groups of T / 2 lanes), samples in front of a tile's first (a multiple of D >= wideband_reach(n_taps) - 1), tile row pitch
+};
+// T, halo and W for a handle's D and n_taps; false when no tile fits (cannot happen within WB_MAX_D, WB_MAX_TAPS)
+bool wideband_geometry(WidebandArgs& a);
+void launch_wideband(const WidebandArgs& a, hipStream_t s);           // the channeliser, then the carry for the next call
 void launch_copy_f4(const void* src, void* dst, size_t n16, int blocks, hipStream_t s);
 void launch_copy_out(const void* src_device, void* dst_host, size_t bytes, hipStream_t s);      // a kernel's stores into page-locked host memory (hipHostMalloc: the same address on the device)
 

@@ -127,6 +127,15 @@ int reset_synchroniser(dabphy_handle* h, bool decoder_too)
     return sync(h);
 }
 
+// the wideband front end's carried state back to the start of a capture: zeros in front of sample 0
+static int wideband_clear(dabphy_handle* h)
+{
+    HIPCHK(h, hipStreamSynchronize(h->copy_stream));          // writes still queued there read and write the carry
+    for (DevBuf& c : h->wb.carry) HIPCHK(h, hipMemsetAsync(c.p, 0, c.cap, h->stream));
+    h->wb.abs = 0; h->wb.carry_sel = 0; h->wb.last_valid = false;
+    return DABPHY_OK;
+}
+
 int dabphy_reset(dabphy_handle* h)
 {
     DeviceBind dev_(h);
@@ -145,6 +154,7 @@ int dabphy_reset(dabphy_handle* h)
     // ... and the frame count starts over: every selected sub-channel's time de-interleaver fills again from the first CIF decoded
     for (auto& c : h->classes) { for (MscPair& p : c.pairs) p.cif0 = -1; int r2 = upload_pairs(h, c); if (r2) return r2; }
     h->tii_ran = false;
+    if (h->wb.on && (r = wideband_clear(h))) return r;
     return sync(h);
 }
 
@@ -156,6 +166,7 @@ int dabphy_stream_bind_device(dabphy_handle* h, const void* d_iq, uint64_t ring_
     h->s_iq = reinterpret_cast<const cf32*>(d_iq); h->s_ring = ring_samples; h->s_stride = stride_samples;
     h->s_valid = n_valid; h->s_enqueued = 0; h->commit_slot = -1; h->s_loop = loop;
     h->s_bounded = false;                                         // the caller's cf32 samples: no bound known
+    h->wb.on = false; h->wb.last_valid = false;                   // a stream bound or opened any other way is no wideband stream
     return dabphy_reset(h);
 }
 
@@ -188,6 +199,7 @@ int dabphy_stream_write(dabphy_handle* h, const float* iq, uint64_t n_samples)
 {
     DeviceBind dev_(h);
     if (!h || !iq || !h->s_iq_own.p || h->s_iq != h->s_iq_own.as<cf32>() || n_samples == 0 || n_samples > h->s_ring) return DABPHY_ERR_INVALID;
+    if (h->wb.on) return DABPHY_ERR_STATE;                        // a wideband stream takes the capture (dabphy_stream_write_wideband)
     h->s_bounded = false;                                         // cf32 from the caller: any magnitude
     // the chain that may be running ahead must not race with the copy
     HIPCHK(h, hipStreamSynchronize(h->sync_stream));
@@ -209,6 +221,7 @@ int dabphy_stream_write_raw(dabphy_handle* h, const void* data, uint64_t n_sampl
     if (format == DABPHY_FMT_CF32) return dabphy_stream_write(h, reinterpret_cast<const float*>(data), n_samples);
     if (!h || !data || !h->s_iq_own.p || h->s_iq != h->s_iq_own.as<cf32>() || n_samples == 0 || n_samples > h->s_ring ||
         format < DABPHY_FMT_U8 || format > DABPHY_FMT_S16BE) return DABPHY_ERR_INVALID;
+    if (h->wb.on) return DABPHY_ERR_STATE;
     const size_t bps = (format == DABPHY_FMT_U8 || format == DABPHY_FMT_S8) ? 2 : 4;
     const uint32_t B = h->cfg.n_ensembles;
     int r;
@@ -240,6 +253,7 @@ int dabphy_stream_write_raw_async(dabphy_handle* h, const void* data, uint64_t n
     DeviceBind dev_(h);
     if (!h || !data || !h->s_iq_own.p || h->s_iq != h->s_iq_own.as<cf32>() || n_samples == 0 || n_samples > h->s_ring ||
         format < DABPHY_FMT_U8 || format > DABPHY_FMT_S16BE) return DABPHY_ERR_INVALID;
+    if (h->wb.on) return DABPHY_ERR_STATE;
     const size_t bps = (format == DABPHY_FMT_U8 || format == DABPHY_FMT_S8) ? 2 : 4;
     const uint32_t B = h->cfg.n_ensembles;
     if (h->s_enqueued < h->s_valid) h->s_enqueued = h->s_valid;            // synchronous writes in between
@@ -256,6 +270,119 @@ int dabphy_stream_write_raw_async(dabphy_handle* h, const void* data, uint64_t n
     HIPCHK(h, hipEventRecord(h->ev_ingest[slot], h->copy_stream));
     h->s_enqueued += n_samples;
     return DABPHY_OK;
+}
+
+// ---- wideband front end: one capture, channelised into every ensemble's ring row (k_wideband.hip)
+static size_t wideband_bps(int32_t format) { return format == DABPHY_FMT_CF32 ? 8 : (format == DABPHY_FMT_U8 || format == DABPHY_FMT_S8) ? 2 : 4; }
+
+int dabphy_stream_open_wideband(dabphy_handle* h, uint64_t ring_samples, const dabphy_wideband_config* cfg)
+{
+    DeviceBind dev_(h);
+    if (!h || !cfg || cfg->struct_size != sizeof(dabphy_wideband_config) || !cfg->taps || !cfg->offset_16khz) return DABPHY_ERR_INVALID;
+    const uint32_t D = cfg->decimation, n_taps = cfg->n_taps, B = h->cfg.n_ensembles;
+    if (D < 1 || D > (uint32_t)WB_MAX_D || n_taps < 1 || n_taps > (uint32_t)WB_MAX_TAPS || cfg->format < DABPHY_FMT_CF32 || cfg->format > DABPHY_FMT_S16BE) return DABPHY_ERR_INVALID;
+    for (uint32_t e = 0; e < B; e++) if (cfg->offset_16khz[e] > 64 * (int32_t)D || cfg->offset_16khz[e] < -64 * (int32_t)D) return DABPHY_ERR_INVALID;
+    WidebandArgs geo{}; geo.D = D; geo.n_taps = n_taps;
+    if (!wideband_geometry(geo)) return DABPHY_ERR_INVALID;
+    int r;
+    if ((r = dabphy_stream_open(h, ring_samples))) return r;     // the ring and the reset; drops an earlier configuration
+    // tables, in double precision, rounded once: the oscillator over its period, every ensemble's offset mod P, its taps turned by +theta k
+    const uint32_t P = 128 * D, e_pad = (B + WB_ENS_STEP - 1) / WB_ENS_STEP * WB_ENS_STEP;
+    const double two_pi = 6.283185307179586476925286766559;
+    std::vector<cf32> osc(P), ctaps((size_t)wideband_reach(n_taps) * e_pad, cf32{0.0f, 0.0f});      // (rows of zeros behind the filter: the kernel fetches whole steps, one ahead)
+    std::vector<uint32_t> om(B);
+    for (uint32_t p = 0; p < P; p++) { const double a = -two_pi * (double)p / (double)P; osc[p].re = (float)cos(a); osc[p].im = (float)sin(a); }
+    for (uint32_t e = 0; e < B; e++) {
+        om[e] = (uint32_t)(((int64_t)cfg->offset_16khz[e] % (int64_t)P + (int64_t)P) % (int64_t)P);
+        for (uint32_t k = 0; k < n_taps; k++) {
+            const double a = two_pi * (double)(((uint64_t)om[e] * k) % P) / (double)P, t = (double)cfg->taps[k];
+            ctaps[(size_t)k * e_pad + e].re = (float)(t * cos(a)); ctaps[(size_t)k * e_pad + e].im = (float)(t * sin(a));
+        }
+    }
+    const size_t carry_bytes = (size_t)std::max<uint32_t>(n_taps - 1, 1) * sizeof(cf32), stage = (size_t)ring_samples * D * wideband_bps(cfg->format);
+    if ((r = ensure(h, h->wb.osc, osc.size() * sizeof(cf32))) || (r = ensure(h, h->wb.ctaps, ctaps.size() * sizeof(cf32))) || (r = ensure(h, h->wb.om, om.size() * sizeof(uint32_t))) ||
+        (r = ensure(h, h->wb.carry[0], carry_bytes)) || (r = ensure(h, h->wb.carry[1], carry_bytes)) ||
+        (r = ensure(h, h->s_raw, stage)) || (r = ensure(h, h->s_raw2[0], stage)) || (r = ensure(h, h->s_raw2[1], stage))) return r;
+    HIPCHK(h, hipMemcpyAsync(h->wb.osc.p, osc.data(), osc.size() * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->wb.ctaps.p, ctaps.data(), ctaps.size() * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->wb.om.p, om.data(), om.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    h->wb.D = D; h->wb.n_taps = n_taps; h->wb.e_pad = e_pad; h->wb.format = cfg->format;
+    h->wb.on = true;
+    h->s_bounded = false;                                         // a FIR's output: no bound known (the sLevel bracket of sync_args relies on one)
+    if ((r = wideband_clear(h))) return r;
+    return sync(h);                                               // (the host tables go out of scope)
+}
+
+// the launch of one write: n capture samples staged at `raw`, outputs from ring position `written` on
+static WidebandArgs wideband_args(dabphy_handle* h, const void* raw, uint64_t n, uint64_t written)
+{
+    WidebandArgs a{};
+    a.D = h->wb.D; a.n_taps = h->wb.n_taps; wideband_geometry(a);
+    a.raw = reinterpret_cast<const uint8_t*>(raw); a.format = h->wb.format; a.n = n; a.n_out = n / h->wb.D;
+    a.carry_in = h->wb.carry[h->wb.carry_sel].as<cf32>(); a.carry_out = h->wb.carry[h->wb.carry_sel ^ 1].as<cf32>();
+    a.ctaps = h->wb.ctaps.as<cf32>(); a.osc = h->wb.osc.as<cf32>(); a.om = h->wb.om.as<uint32_t>();
+    a.iq = h->s_iq_own.as<cf32>(); a.iq_stride = h->s_stride; a.ring = h->s_ring; a.w = written % h->s_ring;
+    a.P = 128 * h->wb.D; a.n_ens = h->cfg.n_ensembles; a.e_pad = h->wb.e_pad; a.abs_mod = (uint32_t)(h->wb.abs % a.P);
+    h->wb.abs += n; if (h->wb.n_taps > 1) h->wb.carry_sel ^= 1;
+    return a;
+}
+static int wideband_write_check(const dabphy_handle* h, const void* data, uint64_t n)
+{
+    if (!h || !data) return DABPHY_ERR_INVALID;
+    if (!h->wb.on || !h->s_iq_own.p || h->s_iq != h->s_iq_own.as<cf32>()) return DABPHY_ERR_STATE;
+    if (n == 0 || n % h->wb.D || n / h->wb.D > h->s_ring) return DABPHY_ERR_INVALID;
+    return DABPHY_OK;
+}
+
+int dabphy_stream_write_wideband(dabphy_handle* h, const void* data, uint64_t n_capture_samples)
+{
+    DeviceBind dev_(h);
+    int r;
+    if ((r = wideband_write_check(h, data, n_capture_samples))) return r;
+    if (h->s_enqueued > h->s_valid) return DABPHY_ERR_STATE;     // asynchronous writes not committed: this one would not continue them
+    HIPCHK(h, hipStreamSynchronize(h->sync_stream));             // the chain that may be running ahead must not race with the write
+    HIPCHK(h, hipStreamSynchronize(h->copy_stream));             // ... and the carry of an asynchronous write in flight comes first
+    HIPCHK(h, hipMemcpyAsync(h->s_raw.p, data, (size_t)n_capture_samples * wideband_bps(h->wb.format), hipMemcpyHostToDevice, h->stream));
+    h->wb.last = wideband_args(h, h->s_raw.p, n_capture_samples, h->s_valid); h->wb.last_valid = true;
+    launch_wideband(h->wb.last, h->stream);
+    h->s_valid += n_capture_samples / h->wb.D;
+    return sync(h);
+}
+
+int dabphy_stream_write_wideband_async(dabphy_handle* h, const void* data, uint64_t n_capture_samples)
+{
+    DeviceBind dev_(h);
+    int r;
+    if ((r = wideband_write_check(h, data, n_capture_samples))) return r;
+    if (h->s_enqueued < h->s_valid) h->s_enqueued = h->s_valid;            // synchronous writes in between
+    const int slot = h->raw_sel; h->raw_sel ^= 1;
+    // the staging slot (and with it the host buffer of the call before last) is free once its previous conversion has run
+    HIPCHK(h, hipEventSynchronize(h->ev_ingest[slot]));
+    HIPCHK(h, hipMemcpyAsync(h->s_raw2[slot].p, data, (size_t)n_capture_samples * wideband_bps(h->wb.format), hipMemcpyHostToDevice, h->copy_stream));
+    launch_wideband(wideband_args(h, h->s_raw2[slot].p, n_capture_samples, h->s_enqueued), h->copy_stream);
+    HIPCHK(h, hipEventRecord(h->ev_ingest[slot], h->copy_stream));
+    h->s_enqueued += n_capture_samples / h->wb.D;
+    return DABPHY_OK;
+}
+
+int dabphy_time_wideband(dabphy_handle* h, uint32_t warmup, uint32_t iters, float* ms)
+{
+    DeviceBind dev_(h);
+    if (!h || !ms || iters == 0) return DABPHY_ERR_INVALID;
+    if (!h->wb.on || !h->wb.last_valid) return DABPHY_ERR_STATE;
+    HIPCHK(h, hipStreamSynchronize(h->sync_stream));
+    HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+    ScopedEvent e0, e1;
+    HIPCHK(h, e0.create()); HIPCHK(h, e1.create());
+    for (uint32_t i = 0; i < warmup; i++) launch_wideband(h->wb.last, h->stream);
+    for (uint32_t i = 0; i < iters; i++) {
+        HIPCHK(h, hipEventRecord(e0, h->stream));
+        launch_wideband(h->wb.last, h->stream);
+        HIPCHK(h, hipEventRecord(e1, h->stream));
+        HIPCHK(h, hipEventSynchronize(e1));
+        HIPCHK(h, hipEventElapsedTime(&ms[i], e0, e1));
+    }
+    return sync(h);
 }
 
 int dabphy_stream_commit(dabphy_handle* h)

@@ -15,20 +15,7 @@ __global__ void __launch_bounds__(256) k_ingest(IngestArgs A)
     const uint8_t* __restrict__ src = A.raw + (size_t)b * A.raw_stride;
     cf32* __restrict__ dst = A.iq + (size_t)b * A.iq_stride;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < A.n; i += (uint64_t)gridDim.x * blockDim.x) {
-        cf32 v;
-        if (A.format == 1) {                                  // U8
-            const uint16_t w = reinterpret_cast<const uint16_t*>(src)[i];
-            v.re = (float)((int)(w & 0xff) - 128) * 0.0078125f; v.im = (float)((int)(w >> 8) - 128) * 0.0078125f;
-        } else if (A.format == 2) {                           // S8
-            const uint16_t w = reinterpret_cast<const uint16_t*>(src)[i];
-            v.re = (float)(int8_t)(w & 0xff) * 0.0078125f; v.im = (float)(int8_t)(w >> 8) * 0.0078125f;
-        } else {                                              // S16 "LE" (3) / "BE" (4)
-            const uint32_t w = reinterpret_cast<const uint32_t*>(src)[i];
-            const uint32_t b0 = w & 0xff, b1 = (w >> 8) & 0xff, b2 = (w >> 16) & 0xff, b3 = w >> 24;
-            const int16_t I = A.format == 3 ? (int16_t)((b0 << 8) | b1) : (int16_t)((b1 << 8) | b0);
-            const int16_t Q = A.format == 3 ? (int16_t)((b2 << 8) | b3) : (int16_t)((b3 << 8) | b2);
-            v.re = (float)I; v.im = (float)Q;
-        }
+        const cf32 v = ingest_sample(src, i, A.format);
         uint64_t p = A.w + i; if (p >= A.ring) p -= A.ring;
         dst[p] = v;
     }

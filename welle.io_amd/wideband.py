@@ -1,0 +1,71 @@
+"""Wideband front end, host side: the low-pass design for dabphy_stream_open_wideband and a synthetic multi-block capture.
+
+A capture at decimation x 2.048 MS/s holds several DAB blocks side by side; the library mixes each one down by its offset (in units of
+16 kHz = 2 048 000 / 128), filters with the real taps given here and keeps every decimation-th sample (include/dabphy.h)."""
+import numpy as np
+
+RATE = 2048000
+OFFSET_UNIT_HZ = RATE // 128            # 16 kHz: every DAB block centre is a multiple of it
+
+
+def design_taps(decimation, taps_per_branch=16, beta=8.0):
+    """Windowed-sinc Kaiser low-pass for a capture at decimation x 2.048 MS/s: taps_per_branch * decimation real taps (float32), unit DC
+    gain, computed in float64.  Cutoff 1.024 MHz: the transition may run from 768 kHz, the edge of the DAB signal, to 1 280 kHz, the
+    lowest frequency that decimation folds onto that edge (1 280 - 2 048 = -768 kHz) -- a neighbour 1.712 MHz away reaches from 944 kHz
+    upwards, and what it has below 1 280 kHz lands outside the carriers.  The cutoff sits in the middle of that band."""
+    decimation = int(decimation); n = int(taps_per_branch) * decimation
+    if decimation < 1 or n < 1:
+        raise ValueError("design_taps: decimation and taps_per_branch must be positive")
+    fc = 1024000.0 / (decimation * float(RATE))              # cycles per capture sample
+    k = np.arange(n, dtype=np.float64) - (n - 1) / 2.0
+    h = 2.0 * fc * np.sinc(2.0 * fc * k) * np.kaiser(n, float(beta))
+    return (h / h.sum()).astype(np.float32)
+
+
+def upsample(x, decimation, pad_to=4096):
+    """x at 2.048 MS/s -> decimation x that rate by zero-padding its spectrum (exact for the band-limited streams of synth.make_stream);
+    the stream is first padded with zeros to a multiple of pad_to samples"""
+    x = np.asarray(x, np.complex128)
+    n = -(-len(x) // pad_to) * pad_to
+    X = np.fft.fft(np.concatenate([x, np.zeros(n - len(x), np.complex128)]))
+    if decimation == 1:
+        return np.fft.ifft(X)
+    Y = np.zeros(n * decimation, np.complex128)
+    Y[:n // 2] = X[:n // 2]; Y[-(n // 2):] = X[n // 2:]
+    return np.fft.ifft(Y) * decimation
+
+
+def oscillator(offset, n, decimation, sign=+1):
+    """exp(sign * 2 pi j * offset * 16 kHz * i / (decimation * 2.048 MHz)) for i < n, from the exact phase (offset * i) mod (128 * decimation)"""
+    P = 128 * int(decimation)
+    ph = (np.arange(n, dtype=np.int64) * int(offset)) % P
+    return np.exp(sign * 2j * np.pi * ph / P)
+
+
+def synth_capture(streams, offsets, decimation, snr_db=None, seed=0, amplitude=0.25):
+    """One capture (complex128, at decimation x 2.048 MS/s) out of noise-free 2.048 MS/s streams (synth.make_stream without snr_db): each
+    is upsampled, shifted up by its offset x 16 kHz, and all are summed; white noise is added so that every channel sees snr_db in ITS
+    2.048 MHz (a signal of power amplitude ** 2: the noise power of the capture is decimation times the channel's).  The length is that
+    of the longest stream, rounded up to a multiple of 4 096, times the decimation."""
+    if len(streams) != len(offsets):
+        raise ValueError("synth_capture: %d streams, %d offsets" % (len(streams), len(offsets)))
+    n = max(len(s) for s in streams)
+    cap = None
+    for s, off in zip(streams, offsets):
+        s = np.concatenate([np.asarray(s, np.complex128), np.zeros(n - len(s), np.complex128)])
+        u = upsample(s, decimation)
+        u *= oscillator(off, len(u), decimation)
+        cap = u if cap is None else cap + u
+    if snr_db is not None:
+        rng = np.random.RandomState(seed)
+        sigma = np.sqrt(decimation * amplitude ** 2 / (10 ** (snr_db / 10.0)) / 2)
+        cap = cap + sigma * (rng.randn(len(cap)) + 1j * rng.randn(len(cap)))
+    return cap
+
+
+def to_u8_capture(cap, headroom=0.99):
+    """-> (u8 array [n][2], the scale applied): the capture scaled so that its largest component sits at `headroom` of full scale --
+    nothing clips -- and quantised as the u8 front ends deliver it ((b - 128) / 128 on the way in)"""
+    scale = headroom / max(np.abs(cap.real).max(), np.abs(cap.imag).max())
+    iq = np.stack([cap.real, cap.imag], 1) * scale
+    return np.clip(np.round(iq * 127.0) + 128, 0, 255).astype(np.uint8), scale
