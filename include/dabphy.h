@@ -60,7 +60,7 @@ uint32_t dabphy_abi_version(void);
 typedef enum { DABPHY_STRUCT_CONFIG = 0, DABPHY_STRUCT_FRAME_INFO = 1, DABPHY_STRUCT_SF_EVENT = 2, DABPHY_STRUCT_SUBCHANNEL = 3,
                DABPHY_STRUCT_PROTECTION = 4, DABPHY_STRUCT_TII_MEASUREMENT = 5, DABPHY_STRUCT_MSC_DESC = 6,
                DABPHY_STRUCT_MP2_EVENT = 7, DABPHY_STRUCT_AU_SERVICE = 8, DABPHY_STRUCT_AU_DESC = 9,
-               DABPHY_STRUCT_WIDEBAND_CONFIG = 10 } dabphy_struct_id;
+               DABPHY_STRUCT_WIDEBAND_CONFIG = 10, DABPHY_STRUCT_RESAMPLER_CONFIG = 11 } dabphy_struct_id;
 size_t dabphy_struct_size(int32_t which);      /* 0 for an unknown id */
 
 /* RadioReceiverOptions (src/backend/radio-receiver-options.h:66-84) + batch geometry */
@@ -260,6 +260,38 @@ typedef struct {
 int dabphy_stream_open_wideband(dabphy_handle* h, uint64_t ring_samples, const dabphy_wideband_config* cfg);
 int dabphy_stream_write_wideband(dabphy_handle* h, const void* data, uint64_t n_capture_samples);
 int dabphy_stream_write_wideband_async(dabphy_handle* h, const void* data, uint64_t n_capture_samples);
+
+/* The same front end for a capture at 2.048 MS/s x M / L, M and L coprime: 2.4 MS/s = 75/64, 8 MS/s = 125/32, 10 MS/s = 625/128,
+ * 56 MS/s = 875/32 ...  With N the absolute capture index since the open call or the last dabphy_reset, ensemble e receives as sample m
+ *     y_e[m] = sum_{j = 0 .. J - 1} h[r_m + j L] * c(x[a_m - j]) * w_e[a_m - j]
+ *     a_m = floor((m M + M - 1) / L),  r_m = (m M + M - 1) mod L,  J = ceil(n_taps / L),  h[k >= n_taps] = 0,  x[i < 0] = 0
+ *     w_e[i] = exp(-2 pi j ((offset_16khz[e] * L * i) mod P) / P),  P = 128 M
+ * h = taps: the caller's real prototype low-pass at L x the capture's rate, tap 0 on the newest sample (the polyphase form of: stuff
+ * L - 1 zeros between samples, filter, keep every M-th).  The phase is exact: 16 kHz x L / (2.048 MHz x M) = L / (128 M) cycles per
+ * capture sample.  With L = 1 this is dabphy_stream_open_wideband's sum with D = M.  After N capture samples the stream holds
+ * floor(N L / M) samples: a write of n appends floor((N + n) L / M) - floor(N L / M), which may be none.  Sums run in fp32, every
+ * output adding j = 0, 1, ... into one accumulator per component; a capture written in any pieces gives the same bits as one written at
+ * once (the samples the sums reach back over, N and the output index are carried from write to write, the indices as exact integers).
+ *   dabphy_stream_open_resampled     dabphy_stream_open (reset included) + the tables; taps and offsets are copied.  Every buffer the
+ *                                    writes need is created here, staging for the largest write -- about (ring_samples + 1) M / L
+ *                                    samples -- included.  DABPHY_ERR_INVALID: a null pointer, struct_size not this library's, L outside
+ *                                    1 .. 512, M outside 1 .. 4096, M < L or M > 32 L, gcd(L, M) != 1, n_taps outside 1 .. 1024 L (1 024
+ *                                    taps per phase), |offset| L > 64 M, an unknown format, ring_samples as for dabphy_stream_open.
+ *   dabphy_stream_write_wideband, dabphy_stream_write_wideband_async   the writes, on a stream opened this way with any positive n.
+ *                                    DABPHY_ERR_INVALID: a null pointer, n = 0, a write that would append more than ring_samples.
+ * Everything else is as for dabphy_stream_open_wideband: plain writes on such a stream and wideband writes on a plain one return
+ * DABPHY_ERR_STATE, so does a synchronous write over uncommitted asynchronous ones; dabphy_reset clears the carry and N and keeps the
+ * configuration; dabphy_stream_open, _bind_device and _upload drop it; the stream counts as unbounded. */
+typedef struct {
+    uint32_t struct_size;           /* sizeof(dabphy_resampler_config) as the CALLER was compiled; fields are only ever appended */
+    uint32_t interpolation;         /* L */
+    uint32_t decimation;            /* M: the capture's rate is 2.048 MS/s x M / L */
+    uint32_t n_taps;                /* prototype taps, at L x the capture's rate */
+    const float* taps;              /* [n_taps] real low-pass, DC gain L for unit gain in the pass band */
+    const int32_t* offset_16khz;    /* [n_ensembles] block centre minus capture centre, in units of 16 kHz */
+    int32_t format;                 /* dabphy_sample_format of the capture */
+} dabphy_resampler_config;
+int dabphy_stream_open_resampled(dabphy_handle* h, uint64_t ring_samples, const dabphy_resampler_config* cfg);
 
 /* diagnostics: n samples of ensemble `ensemble` starting at absolute sample index `pos`, as they lie in the ring (cf32), e.g. to
  * compare the device's format conversion with CRAWFile::convertSamples */

@@ -35,7 +35,7 @@ int dabphy_test_traceback_split(dabphy_handle* h, int32_t on);
  *   second.  What the device's HBM delivers to the simplest possible kernel on this box: the measured denominator bench.py prints
  *   next to the 8 TB/s specification (tools/ubench/copy_f4.hip is the stand-alone sweep of the same kernel). */
 int dabphy_time_copy(dabphy_handle* h, uint64_t bytes, uint32_t blocks_per_cu, uint32_t iters, float* gbytes_per_s);
-/* dabphy_time_wideband: the channeliser's launches of the last dabphy_stream_write_wideband (k_wideband + k_wideband_carry) run again
+/* dabphy_time_wideband: the channeliser's launches of the last dabphy_stream_write_wideband (k_wideband + k_wideband_carry; on a stream opened with dabphy_stream_open_resampled, k_resample + k_resample_carry) run again
  *   on its staged capture, which is still on the device: `warmup` passes, then `iters` timed one by one; ms[i] = device time of pass i.
  *   The passes rewrite the same ring samples with the same values and leave the stream's state alone.  DABPHY_ERR_STATE when no
  *   synchronous wideband write has been made since the open call. */

@@ -1,0 +1,65 @@
+"""Execution-model suite: the wideband front end at a rational rate (one capture at 2.048 MS/s x M / L resampled into the batch's
+ensembles) against the float64 model of tests/resample_model.py and, end to end, against the oracle on each ensemble's direct stream.
+Cases: tests/resample_cases.py."""
+import pytest
+
+import resample_cases as RC
+from conftest import EMU_LIB
+from welle_io_amd import capi
+
+
+def factory(**kw):
+    return capi.DabPhy(lib_path=EMU_LIB, **kw)
+
+
+@pytest.mark.parametrize("L,M,n_taps", RC.SHAPES)
+def test_filter_and_oscillator_vs_model(emu, L, M, n_taps):
+    RC.check_filter_vs_model(factory, L, M, n_taps, "u8")
+
+
+@pytest.mark.parametrize("fmt", [f for f in RC.FORMATS if f != "u8"])
+def test_sample_formats_vs_model(emu, fmt):
+    RC.check_filter_vs_model(factory, 32, 125, 500, fmt)
+
+
+def test_chunking_is_bit_identical(emu):
+    RC.check_chunking(factory)
+
+
+def test_phase_over_a_long_run(emu):
+    RC.check_phase_long_run(factory)
+
+
+def test_ring_wrap(emu):
+    RC.check_ring_wrap(factory)
+
+
+def test_reset_keeps_the_configuration_and_clears_the_carry(emu):
+    RC.check_reset(factory)
+
+
+def test_nothing_left_behind(emu):
+    """every buffer the front end creates goes with the handle (the execution model counts what is alive)"""
+    import ctypes as C
+    import numpy as np
+
+    def live():
+        out = (C.c_int64 * 4)(); C.CDLL(EMU_LIB).hipemu_live_counts(out); return tuple(out)
+    before = live()
+    raw, taps, offsets = RC.filter_case(32, 125, 500, "u8")
+    d = factory(n_ensembles=3, max_frames=1, want_constellation=False)
+    d.stream_open_resampled(RC.RING_MIN, 32, 125, taps, offsets, "u8")
+    d.stream_write_wideband(raw)
+    d.stream_write_wideband_async(np.ascontiguousarray(raw[:64])); d.stream_commit()
+    d.stream_open_resampled(RC.RING_MIN, 2, 3, taps[:7], RC.filter_offsets(2, 3), "s16le")      # a second open reuses or replaces, never leaks
+    d.stream_open_wideband(RC.RING_MIN, 2, taps[:32], [0, 1, -1], "u8")                          # ... nor does the other kind
+    d.close()
+    assert live() == before
+
+
+def test_limits_and_state_errors(emu):
+    RC.check_errors(factory)
+
+
+def test_end_to_end_vs_oracle_on_the_direct_streams(emu):
+    RC.check_end_to_end(factory, L=32, Mx=125, n_taps=2000, offsets=(-107, 0, 107))

@@ -27,6 +27,12 @@ class WidebandConfig(C.Structure):
                 ("offset_16khz", C.POINTER(C.c_int32)), ("format", C.c_int32)]
 
 
+class ResamplerConfig(C.Structure):
+    """dabphy_resampler_config"""
+    _fields_ = [("struct_size", C.c_uint32), ("interpolation", C.c_uint32), ("decimation", C.c_uint32), ("n_taps", C.c_uint32),
+                ("taps", C.POINTER(C.c_float)), ("offset_16khz", C.POINTER(C.c_int32)), ("format", C.c_int32)]
+
+
 FORMATS = {"cf32": 0, "u8": 1, "s8": 2, "s16le": 3, "s16be": 4}              # dabphy_sample_format
 FORMAT_BYTES = {0: 8, 1: 2, 2: 2, 3: 4, 4: 4}                                # per complex sample
 
@@ -538,8 +544,21 @@ class DabPhy:
         self._chk(self.lib.dabphy_stream_open_wideband(self.h, C.c_uint64(ring_samples), C.byref(cfg)))
         self._wb = (int(decimation), FORMAT_BYTES[FORMATS[fmt]])
 
+    def stream_open_resampled(self, ring_samples, interpolation, decimation, taps, offsets, fmt):
+        """the same for a capture at 2.048 MS/s x decimation / interpolation (coprime): taps = the real prototype low-pass at
+        interpolation x the capture's rate (wideband.design_taps_rational); writes go through stream_write_wideband[_async], any
+        positive number of samples at a time (dabphy_stream_open_resampled)"""
+        taps = np.ascontiguousarray(taps, np.float32).reshape(-1); offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        if len(offsets) != self.cfg.n_ensembles:
+            raise DabPhyError("stream_open_resampled: %d offsets for %d ensembles" % (len(offsets), self.cfg.n_ensembles))
+        cfg = ResamplerConfig(C.sizeof(ResamplerConfig), int(interpolation), int(decimation), len(taps), taps.ctypes.data_as(C.POINTER(C.c_float)),
+                              offsets.ctypes.data_as(C.POINTER(C.c_int32)), FORMATS[fmt])
+        self._chk(self.lib.dabphy_stream_open_resampled(self.h, C.c_uint64(ring_samples), C.byref(cfg)))
+        self._wb = ((int(interpolation), int(decimation)), FORMAT_BYTES[FORMATS[fmt]])
+
     def stream_write_wideband(self, data):
-        """data: the capture's next samples, [n][2] integers of the configured format (or complex64); n a multiple of the decimation"""
+        """data: the capture's next samples, [n][2] integers of the configured format (or complex64); n a multiple of the decimation
+        (any positive n on a stream opened with stream_open_resampled)"""
         data = np.ascontiguousarray(data)
         self._chk(self.lib.dabphy_stream_write_wideband(self.h, _p(data), C.c_uint64(data.nbytes // self._wb[1])))
 

@@ -20,6 +20,7 @@ size_t dabphy_struct_size(int32_t which)
         case DABPHY_STRUCT_AU_SERVICE: return sizeof(dabphy_au_service);
         case DABPHY_STRUCT_AU_DESC: return sizeof(dabphy_au_desc);
         case DABPHY_STRUCT_WIDEBAND_CONFIG: return sizeof(dabphy_wideband_config);
+        case DABPHY_STRUCT_RESAMPLER_CONFIG: return sizeof(dabphy_resampler_config);
     }
     return 0;
 }

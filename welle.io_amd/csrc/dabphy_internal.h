@@ -139,6 +139,13 @@ struct dabphy_handle {
         DevBuf ctaps, osc, om, carry[2]; int carry_sel = 0;      // carry[carry_sel] lies in front of the next write
         uint64_t abs = 0;                                        // capture samples written since the open / reset
         WidebandArgs last{}; bool last_valid = false;            // the last synchronous write as it was launched (dabphy_time_wideband runs it again)
+        // ... or at 2.048 MS/s x M / L (dabphy_stream_open_resampled; k_resample.hip): the same two write calls, carries and staging
+        // buffers.  Exact integers carried from write to write: `abs` = N, and frac = (N L) mod M -- the stream holds (N L - frac) / M
+        // outputs, and M - 1 - frac says where the next one's newest sample lies and which phase it has
+        bool rational = false;
+        uint32_t L = 0, M = 0, J = 0; uint64_t frac = 0, stage_samples = 0;
+        DevBuf rs_taps, rs_osc_lo;                               // [J + RS_TAP_STEP][L]; [n_ens][RS_OSC_LO] (`osc` holds [n_ens][n_hi]; ctaps and om are the integer path's)
+        ResampleArgs rs_last{};
     } wb;
     // bulk MSC drain (dabphy_msc_drain_begin / _wait): the class outputs leave on a stream of their own while the next batch starts
     hipStream_t drain_stream = nullptr; hipEvent_t ev_drain_done = nullptr, ev_drain_staged = nullptr; bool drain_pending = false; DevBuf drain_stage;

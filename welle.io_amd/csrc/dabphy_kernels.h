@@ -322,6 +322,31 @@ struct WidebandArgs {
 // T, halo and W for a handle's D and n_taps; false when no tile fits (cannot happen within WB_MAX_D, WB_MAX_TAPS)
 bool wideband_geometry(WidebandArgs& a);
 void launch_wideband(const WidebandArgs& a, hipStream_t s);           // the channeliser, then the carry for the next call
+
+// Rational resampler (k_resample.hip): one capture at 2.048 MS/s x M / L -> the ring rows of the handle's ensembles.  With m the output's
+// index since the open call / reset, a_m = (m M + M - 1) div L its newest capture sample and r_m = (m M + M - 1) mod L its phase,
+//   y_e[m] = sum_j taps[j][r_m] * (c(x[a_m - j]) * w_e[(a_m - j) mod P]),   P = 128 M
+//   w_e[hi RS_OSC_LO + lo] = osc_hi[e][hi] * osc_lo[e][lo],   osc_hi[e][hi] = exp(-2 pi j ((offset_e L hi RS_OSC_LO) mod P) / P),  osc_lo[e][lo] likewise for lo
+// with taps[j][r] = h[r + j L] (zeros from n_taps on and up to J rows, whole RS_TAP_STEPs); all three tables are made by the
+// host in double precision (dabphy_stream_open_resampled).  Every output adds j = 0 ... J - 1 in that order with fmaf, wherever it falls
+// in a call or in a tile.  N, the output index and the phase are 64-bit integers of the HOST; the kernel sees residues only.
+constexpr int RS_MAX_L = 512, RS_MAX_M = 4096, RS_MAX_RATIO = 32, RS_MAX_TAPS_PER_PHASE = 1024;
+constexpr int RS_TAP_STEP = 4;                                       // taps a lane has in flight while it adds the four before
+constexpr int RS_OSC_LO = 256;                                       // radix of the oscillator's two tables
+constexpr int RS_MIX_STEP = 4;                                       // span entries a thread converts and mixes per turn, their loads in flight together
+constexpr int RS_TILE_SMALL = 2560, RS_TILE_MID = 4864, RS_TILE_LARGE = 8192;   // samples of LDS the kernel's builds hold (8, 4, 2 work-groups per compute unit)
+struct ResampleArgs {
+    const uint8_t* raw; int format; uint64_t n, n_out;    // the call's capture: n samples, n_out outputs (may be 0: only the carry moves)
+    const cf32* carry_in; cf32* carry_out;                // the J - 1 converted samples in front of the call / behind it (two buffers, swapped by the host)
+    const float* taps; const cf32* osc_hi; const cf32* osc_lo; uint32_t n_hi;   // [J + RS_TAP_STEP][L], [n_ens][n_hi] with n_hi = ceil(P / RS_OSC_LO), [n_ens][RS_OSC_LO]
+    cf32* iq; size_t iq_stride; uint64_t ring, w;         // output 0 of the call goes to ring position w of every row
+    uint32_t L, M, J, P, n_ens;                           // J: taps per phase as the kernel adds them, a multiple of RS_TAP_STEP
+    uint32_t a0, r0, abs_mod;                             // the call's first output: index in the call of its newest sample, its phase; absolute index of the call's sample 0, mod P
+    uint32_t T, G, Q, W, S;                               // outputs per tile = threads per work-group; ensembles per pass; span layout: entry s at (s mod Q) W + s div Q; entries per span
+};
+// T, G, Q, W and S for a handle's L, M and J; false when no tile fits (cannot happen within the limits above)
+bool resample_geometry(ResampleArgs& a);
+void launch_resample(const ResampleArgs& a, hipStream_t s);           // the resampler (when the call has outputs), then the carry for the next call
 void launch_copy_f4(const void* src, void* dst, size_t n16, int blocks, hipStream_t s);
 void launch_copy_out(const void* src_device, void* dst_host, size_t bytes, hipStream_t s);      // a kernel's stores into page-locked host memory (hipHostMalloc: the same address on the device)
 

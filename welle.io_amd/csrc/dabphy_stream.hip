@@ -132,7 +132,7 @@ static int wideband_clear(dabphy_handle* h)
 {
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));          // writes still queued there read and write the carry
     for (DevBuf& c : h->wb.carry) HIPCHK(h, hipMemsetAsync(c.p, 0, c.cap, h->stream));
-    h->wb.abs = 0; h->wb.carry_sel = 0; h->wb.last_valid = false;
+    h->wb.abs = 0; h->wb.frac = 0; h->wb.carry_sel = 0; h->wb.last_valid = false;
     return DABPHY_OK;
 }
 
@@ -307,10 +307,77 @@ int dabphy_stream_open_wideband(dabphy_handle* h, uint64_t ring_samples, const d
     HIPCHK(h, hipMemcpyAsync(h->wb.ctaps.p, ctaps.data(), ctaps.size() * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->wb.om.p, om.data(), om.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     h->wb.D = D; h->wb.n_taps = n_taps; h->wb.e_pad = e_pad; h->wb.format = cfg->format;
-    h->wb.on = true;
+    h->wb.on = true; h->wb.rational = false;
     h->s_bounded = false;                                         // a FIR's output: no bound known (the sLevel bracket of sync_args relies on one)
     if ((r = wideband_clear(h))) return r;
     return sync(h);                                               // (the host tables go out of scope)
+}
+
+// ---- ... at 2.048 MS/s x M / L (k_resample.hip)
+static uint32_t gcd_u32(uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; }
+
+int dabphy_stream_open_resampled(dabphy_handle* h, uint64_t ring_samples, const dabphy_resampler_config* cfg)
+{
+    DeviceBind dev_(h);
+    if (!h || !cfg || cfg->struct_size != sizeof(dabphy_resampler_config) || !cfg->taps || !cfg->offset_16khz) return DABPHY_ERR_INVALID;
+    const uint32_t L = cfg->interpolation, M = cfg->decimation, n_taps = cfg->n_taps, B = h->cfg.n_ensembles;
+    if (L < 1 || L > (uint32_t)RS_MAX_L || M < 1 || M > (uint32_t)RS_MAX_M || M < L || M > (uint32_t)RS_MAX_RATIO * L || gcd_u32(L, M) != 1 ||
+        n_taps < 1 || n_taps > (uint32_t)RS_MAX_TAPS_PER_PHASE * L || cfg->format < DABPHY_FMT_CF32 || cfg->format > DABPHY_FMT_S16BE) return DABPHY_ERR_INVALID;
+    for (uint32_t e = 0; e < B; e++) if (std::abs((int64_t)cfg->offset_16khz[e]) * (int64_t)L > 64 * (int64_t)M) return DABPHY_ERR_INVALID;
+    // taps per phase as the kernel adds them: whole fetch steps (zero taps behind a phase's last)
+    const uint32_t J = ((n_taps + L - 1) / L + RS_TAP_STEP - 1) / RS_TAP_STEP * RS_TAP_STEP;
+    ResampleArgs geo{}; geo.L = L; geo.M = M; geo.J = J;
+    if (!resample_geometry(geo)) return DABPHY_ERR_INVALID;
+    int r;
+    if ((r = dabphy_stream_open(h, ring_samples))) return r;     // the ring and the reset; drops an earlier configuration
+    // tables, in double precision, rounded once: every ensemble's oscillator at the multiples of RS_OSC_LO and at the RS_OSC_LO indices below
+    // one, each from the exact phase (offset L i) mod P -- the product exceeds 2^32; the prototype
+    const uint32_t P = 128 * M;
+    const double two_pi = 6.283185307179586476925286766559;
+    const uint32_t n_hi = (P + RS_OSC_LO - 1) / RS_OSC_LO;
+    std::vector<cf32> osc_hi((size_t)B * n_hi), osc_lo((size_t)B * RS_OSC_LO);
+    std::vector<float> taps((size_t)(J + RS_TAP_STEP) * L, 0.0f);     // [j][r] = h[r + j L]: the prototype as it is, zeros up to J rows and one more fetch step
+    const auto turn = [&](uint64_t step, uint64_t i) { const double a = -two_pi * (double)((step * i) % P) / (double)P; return cf32{(float)cos(a), (float)sin(a)}; };
+    for (uint32_t e = 0; e < B; e++) {
+        const uint64_t step = (uint64_t)((((int64_t)cfg->offset_16khz[e] * (int64_t)L) % (int64_t)P + (int64_t)P) % (int64_t)P);
+        for (uint32_t hi = 0; hi < n_hi; hi++) osc_hi[(size_t)e * n_hi + hi] = turn(step, (uint64_t)hi * RS_OSC_LO);
+        for (uint32_t lo = 0; lo < (uint32_t)RS_OSC_LO; lo++) osc_lo[(size_t)e * RS_OSC_LO + lo] = turn(step, lo);
+    }
+    for (uint32_t k = 0; k < n_taps; k++) taps[k] = cfg->taps[k];
+    // the largest write the ring takes: fewer than (ring + 1) M / L samples
+    const uint64_t stage_samples = (ring_samples + 1) * M / L + 1;
+    const size_t carry_bytes = (size_t)(J - 1) * sizeof(cf32), stage = (size_t)stage_samples * wideband_bps(cfg->format);
+    if ((r = ensure(h, h->wb.osc, osc_hi.size() * sizeof(cf32))) || (r = ensure(h, h->wb.rs_taps, taps.size() * sizeof(float))) || (r = ensure(h, h->wb.rs_osc_lo, osc_lo.size() * sizeof(cf32))) ||
+        (r = ensure(h, h->wb.carry[0], carry_bytes)) || (r = ensure(h, h->wb.carry[1], carry_bytes)) ||
+        (r = ensure(h, h->s_raw, stage)) || (r = ensure(h, h->s_raw2[0], stage)) || (r = ensure(h, h->s_raw2[1], stage))) return r;
+    HIPCHK(h, hipMemcpyAsync(h->wb.osc.p, osc_hi.data(), osc_hi.size() * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->wb.rs_taps.p, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->wb.rs_osc_lo.p, osc_lo.data(), osc_lo.size() * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
+    h->wb.L = L; h->wb.M = M; h->wb.J = J; h->wb.n_taps = n_taps; h->wb.format = cfg->format; h->wb.stage_samples = stage_samples;
+    h->wb.on = true; h->wb.rational = true;
+    h->s_bounded = false;                                         // a FIR's output: no bound known
+    if ((r = wideband_clear(h))) return r;
+    return sync(h);                                               // (the host tables go out of scope)
+}
+
+// outputs a write of n capture samples appends to a resampled stream: floor((N + n) L / M) - floor(N L / M), from frac = (N L) mod M
+static uint64_t resample_outputs(const dabphy_handle* h, uint64_t n) { return (h->wb.frac + n * h->wb.L) / h->wb.M; }
+
+// the launch of one write to a resampled stream, as wideband_args below
+static ResampleArgs resample_args(dabphy_handle* h, const void* raw, uint64_t n, uint64_t written)
+{
+    ResampleArgs a{};
+    a.L = h->wb.L; a.M = h->wb.M; a.J = h->wb.J; resample_geometry(a);
+    a.raw = reinterpret_cast<const uint8_t*>(raw); a.format = h->wb.format; a.n = n; a.n_out = resample_outputs(h, n);
+    a.carry_in = h->wb.carry[h->wb.carry_sel].as<cf32>(); a.carry_out = h->wb.carry[h->wb.carry_sel ^ 1].as<cf32>();
+    a.taps = h->wb.rs_taps.as<float>(); a.osc_hi = h->wb.osc.as<cf32>(); a.osc_lo = h->wb.rs_osc_lo.as<cf32>();
+    a.iq = h->s_iq_own.as<cf32>(); a.iq_stride = h->s_stride; a.ring = h->s_ring; a.w = written % h->s_ring;
+    a.P = 128 * h->wb.M; a.n_hi = (a.P + RS_OSC_LO - 1) / RS_OSC_LO; a.n_ens = h->cfg.n_ensembles; a.abs_mod = (uint32_t)(h->wb.abs % a.P);
+    // the next output m = (N L - frac) / M: m M + M - 1 = N L + (M - 1 - frac), so its newest sample is N + (M - 1 - frac) div L
+    const uint64_t ahead = h->wb.M - 1 - h->wb.frac;
+    a.a0 = (uint32_t)(ahead / h->wb.L); a.r0 = (uint32_t)(ahead % h->wb.L);
+    h->wb.abs += n; h->wb.frac = (h->wb.frac + n * h->wb.L) % h->wb.M; h->wb.carry_sel ^= 1;
+    return a;
 }
 
 // the launch of one write: n capture samples staged at `raw`, outputs from ring position `written` on
@@ -330,9 +397,25 @@ static int wideband_write_check(const dabphy_handle* h, const void* data, uint64
 {
     if (!h || !data) return DABPHY_ERR_INVALID;
     if (!h->wb.on || !h->s_iq_own.p || h->s_iq != h->s_iq_own.as<cf32>()) return DABPHY_ERR_STATE;
+    if (h->wb.rational) return n == 0 || n >= h->wb.stage_samples || resample_outputs(h, n) > h->s_ring ? DABPHY_ERR_INVALID : DABPHY_OK;
     if (n == 0 || n % h->wb.D || n / h->wb.D > h->s_ring) return DABPHY_ERR_INVALID;
     return DABPHY_OK;
 }
+// queues one write's launches on `s` and says how many outputs they append; `keep`: dabphy_time_wideband runs these launches again
+static uint64_t wideband_launch(dabphy_handle* h, const void* raw, uint64_t n, uint64_t written, hipStream_t s, bool keep)
+{
+    if (h->wb.rational) {
+        const ResampleArgs a = resample_args(h, raw, n, written);
+        if (keep) { h->wb.rs_last = a; h->wb.last_valid = true; }
+        launch_resample(a, s);
+        return a.n_out;
+    }
+    const WidebandArgs a = wideband_args(h, raw, n, written);
+    if (keep) { h->wb.last = a; h->wb.last_valid = true; }
+    launch_wideband(a, s);
+    return a.n_out;
+}
+static void wideband_launch_last(dabphy_handle* h) { if (h->wb.rational) launch_resample(h->wb.rs_last, h->stream); else launch_wideband(h->wb.last, h->stream); }
 
 int dabphy_stream_write_wideband(dabphy_handle* h, const void* data, uint64_t n_capture_samples)
 {
@@ -343,9 +426,7 @@ int dabphy_stream_write_wideband(dabphy_handle* h, const void* data, uint64_t n_
     HIPCHK(h, hipStreamSynchronize(h->sync_stream));             // the chain that may be running ahead must not race with the write
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));             // ... and the carry of an asynchronous write in flight comes first
     HIPCHK(h, hipMemcpyAsync(h->s_raw.p, data, (size_t)n_capture_samples * wideband_bps(h->wb.format), hipMemcpyHostToDevice, h->stream));
-    h->wb.last = wideband_args(h, h->s_raw.p, n_capture_samples, h->s_valid); h->wb.last_valid = true;
-    launch_wideband(h->wb.last, h->stream);
-    h->s_valid += n_capture_samples / h->wb.D;
+    h->s_valid += wideband_launch(h, h->s_raw.p, n_capture_samples, h->s_valid, h->stream, true);
     return sync(h);
 }
 
@@ -359,9 +440,9 @@ int dabphy_stream_write_wideband_async(dabphy_handle* h, const void* data, uint6
     // the staging slot (and with it the host buffer of the call before last) is free once its previous conversion has run
     HIPCHK(h, hipEventSynchronize(h->ev_ingest[slot]));
     HIPCHK(h, hipMemcpyAsync(h->s_raw2[slot].p, data, (size_t)n_capture_samples * wideband_bps(h->wb.format), hipMemcpyHostToDevice, h->copy_stream));
-    launch_wideband(wideband_args(h, h->s_raw2[slot].p, n_capture_samples, h->s_enqueued), h->copy_stream);
+    const uint64_t n_out = wideband_launch(h, h->s_raw2[slot].p, n_capture_samples, h->s_enqueued, h->copy_stream, false);
     HIPCHK(h, hipEventRecord(h->ev_ingest[slot], h->copy_stream));
-    h->s_enqueued += n_capture_samples / h->wb.D;
+    h->s_enqueued += n_out;
     return DABPHY_OK;
 }
 
@@ -374,10 +455,10 @@ int dabphy_time_wideband(dabphy_handle* h, uint32_t warmup, uint32_t iters, floa
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
     ScopedEvent e0, e1;
     HIPCHK(h, e0.create()); HIPCHK(h, e1.create());
-    for (uint32_t i = 0; i < warmup; i++) launch_wideband(h->wb.last, h->stream);
+    for (uint32_t i = 0; i < warmup; i++) wideband_launch_last(h);
     for (uint32_t i = 0; i < iters; i++) {
         HIPCHK(h, hipEventRecord(e0, h->stream));
-        launch_wideband(h->wb.last, h->stream);
+        wideband_launch_last(h);
         HIPCHK(h, hipEventRecord(e1, h->stream));
         HIPCHK(h, hipEventSynchronize(e1));
         HIPCHK(h, hipEventElapsedTime(&ms[i], e0, e1));

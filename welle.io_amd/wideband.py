@@ -1,7 +1,8 @@
 """Wideband front end, host side: the low-pass design for dabphy_stream_open_wideband and a synthetic multi-block capture.
 
 A capture at decimation x 2.048 MS/s holds several DAB blocks side by side; the library mixes each one down by its offset (in units of
-16 kHz = 2 048 000 / 128), filters with the real taps given here and keeps every decimation-th sample (include/dabphy.h)."""
+16 kHz = 2 048 000 / 128), filters with the real taps given here and keeps every decimation-th sample (include/dabphy.h).  The
+*_rational functions are the same for a capture at 2.048 MS/s x decimation / interpolation (dabphy_stream_open_resampled)."""
 import numpy as np
 
 RATE = 2048000
@@ -60,6 +61,45 @@ def synth_capture(streams, offsets, decimation, snr_db=None, seed=0, amplitude=0
         rng = np.random.RandomState(seed)
         sigma = np.sqrt(decimation * amplitude ** 2 / (10 ** (snr_db / 10.0)) / 2)
         cap = cap + sigma * (rng.randn(len(cap)) + 1j * rng.randn(len(cap)))
+    return cap
+
+
+def design_taps_rational(interpolation, decimation, periods=16, beta=8.0):
+    """The prototype for dabphy_stream_open_resampled, a capture at 2.048 MS/s x decimation / interpolation: a windowed-sinc Kaiser
+    low-pass at interpolation x the capture's rate = decimation x 2.048 MS/s, round(periods * decimation) real taps (float32) -- `periods`
+    output samples long, about periods * decimation / interpolation taps per phase.  Cutoff 1.024 MHz as design_taps, DC gain
+    `interpolation` (every phase then has gain about 1), computed in float64."""
+    L, M = int(interpolation), int(decimation); n = int(round(periods * M))
+    if L < 1 or M < L or n < 1:
+        raise ValueError("design_taps_rational: needs 1 <= interpolation <= decimation and a positive length")
+    fc = 1024000.0 / (M * float(RATE))                        # cycles per sample of the prototype's rate
+    k = np.arange(n, dtype=np.float64) - (n - 1) / 2.0
+    h = 2.0 * fc * np.sinc(2.0 * fc * k) * np.kaiser(n, float(beta))
+    return (h * (L / h.sum())).astype(np.float32)
+
+
+def synth_capture_rational(streams, offsets, interpolation, decimation, snr_db=None, seed=0, amplitude=0.25):
+    """synth_capture at 2.048 MS/s x decimation / interpolation: every stream's spectrum (padded to n points, a multiple of 4 096 and
+    of the interpolation) is zero-padded to n * decimation / interpolation points, the stream shifted up by its offset x 16 kHz --
+    (offset * interpolation * i) mod P of P = 128 * decimation cycles at capture sample i -- and white noise of decimation /
+    interpolation times the channel's power added, so that every channel sees snr_db in ITS 2.048 MHz."""
+    L, M = int(interpolation), int(decimation)
+    if len(streams) != len(offsets):
+        raise ValueError("synth_capture_rational: %d streams, %d offsets" % (len(streams), len(offsets)))
+    unit = 4096 * L // np.gcd(4096, L)
+    n = -(-max(len(s) for s in streams) // unit) * unit
+    n2 = n // L * M; P = 128 * M
+    cap = np.zeros(n2, np.complex128)
+    i = np.arange(n2, dtype=np.int64)
+    for s, off in zip(streams, offsets):
+        X = np.fft.fft(np.concatenate([np.asarray(s, np.complex128), np.zeros(n - len(s), np.complex128)]))
+        Y = np.zeros(n2, np.complex128)
+        Y[:n // 2] = X[:n // 2]; Y[-(n // 2):] = X[n // 2:]
+        cap += np.fft.ifft(Y) * (n2 / n) * np.exp(2j * np.pi * ((int(off) * L * i) % P) / P)
+    if snr_db is not None:
+        rng = np.random.RandomState(seed)
+        sigma = np.sqrt(M / L * amplitude ** 2 / (10 ** (snr_db / 10.0)) / 2)
+        cap = cap + sigma * (rng.randn(n2) + 1j * rng.randn(n2))
     return cap
 
 
