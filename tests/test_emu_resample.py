@@ -1,41 +1,43 @@
 """Execution-model suite: the wideband front end at a rational rate (one capture at 2.048 MS/s x M / L resampled into the batch's
 ensembles) against the float64 model of tests/resample_model.py and, end to end, against the oracle on each ensemble's direct stream.
-Cases: tests/resample_cases.py."""
+Cases: tests/frontend_cases.py."""
 import pytest
 
-import resample_cases as RC
+import frontend_cases as F
 from conftest import EMU_LIB
 from welle_io_amd import capi
+
+K = F.RATIONAL                           # the kind's default shapes
 
 
 def factory(**kw):
     return capi.DabPhy(lib_path=EMU_LIB, **kw)
 
 
-@pytest.mark.parametrize("L,M,n_taps", RC.SHAPES)
+@pytest.mark.parametrize("L,M,n_taps", F.RATIONAL_SHAPES)
 def test_filter_and_oscillator_vs_model(emu, L, M, n_taps):
-    RC.check_filter_vs_model(factory, L, M, n_taps, "u8")
+    F.check_filter_vs_model(factory, F.Rational(L, M), n_taps, "u8")
 
 
-@pytest.mark.parametrize("fmt", [f for f in RC.FORMATS if f != "u8"])
+@pytest.mark.parametrize("fmt", [f for f in F.FORMATS if f != "u8"])
 def test_sample_formats_vs_model(emu, fmt):
-    RC.check_filter_vs_model(factory, 32, 125, 500, fmt)
+    F.check_filter_vs_model(factory, K["rate"], K["n_taps"], fmt)
 
 
 def test_chunking_is_bit_identical(emu):
-    RC.check_chunking(factory)
+    F.check_chunking(factory, K["rate"], K["n_taps"])
 
 
 def test_phase_over_a_long_run(emu):
-    RC.check_phase_long_run(factory)
+    F.check_phase_long_run(factory, **K["long_run"])
 
 
 def test_ring_wrap(emu):
-    RC.check_ring_wrap(factory)
+    F.check_ring_wrap(factory, **K["wrap"])
 
 
 def test_reset_keeps_the_configuration_and_clears_the_carry(emu):
-    RC.check_reset(factory)
+    F.check_reset(factory, K["rate"], K["n_taps"], K["reset_n1"])
 
 
 def test_nothing_left_behind(emu):
@@ -46,20 +48,20 @@ def test_nothing_left_behind(emu):
     def live():
         out = (C.c_int64 * 4)(); C.CDLL(EMU_LIB).hipemu_live_counts(out); return tuple(out)
     before = live()
-    raw, taps, offsets = RC.filter_case(32, 125, 500, "u8")
+    raw, taps, offsets = F.filter_case(K["rate"], K["n_taps"], "u8")
     d = factory(n_ensembles=3, max_frames=1, want_constellation=False)
-    d.stream_open_resampled(RC.RING_MIN, 32, 125, taps, offsets, "u8")
+    d.stream_open_resampled(F.RING_MIN, 32, 125, taps, offsets, "u8")
     d.stream_write_wideband(raw)
     d.stream_write_wideband_async(np.ascontiguousarray(raw[:64])); d.stream_commit()
-    d.stream_open_resampled(RC.RING_MIN, 2, 3, taps[:7], RC.filter_offsets(2, 3), "s16le")      # a second open reuses or replaces, never leaks
-    d.stream_open_wideband(RC.RING_MIN, 2, taps[:32], [0, 1, -1], "u8")                          # ... nor does the other kind
+    d.stream_open_resampled(F.RING_MIN, 2, 3, taps[:7], F.Rational(2, 3).filter_offsets(), "s16le")      # a second open reuses or replaces, never leaks
+    d.stream_open_wideband(F.RING_MIN, 2, taps[:32], [0, 1, -1], "u8")                          # ... nor does the other kind
     d.close()
     assert live() == before
 
 
 def test_limits_and_state_errors(emu):
-    RC.check_errors(factory)
+    F.check_errors(factory, K["rate"], K["n_taps"])
 
 
 def test_end_to_end_vs_oracle_on_the_direct_streams(emu):
-    RC.check_end_to_end(factory, L=32, Mx=125, n_taps=2000, offsets=(-107, 0, 107))
+    F.check_end_to_end(factory, F.Rational(32, 125), n_taps=2000, offsets=(-107, 0, 107))

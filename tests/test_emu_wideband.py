@@ -1,40 +1,42 @@
 """Execution-model suite: the wideband front end (one capture channelised into the batch's ensembles) against the float64 model of
-tests/wideband_model.py and, end to end, against the oracle on each ensemble's direct stream.  Cases: tests/wideband_cases.py."""
+tests/wideband_model.py and, end to end, against the oracle on each ensemble's direct stream.  Cases: tests/frontend_cases.py."""
 import pytest
 
-import wideband_cases as W
+import frontend_cases as F
 from conftest import EMU_LIB
 from welle_io_amd import capi
+
+K = F.INTEGER                           # the kind's default shapes
 
 
 def factory(**kw):
     return capi.DabPhy(lib_path=EMU_LIB, **kw)
 
 
-@pytest.mark.parametrize("D,n_taps", W.SHAPES)
+@pytest.mark.parametrize("D,n_taps", F.INTEGER_SHAPES)
 def test_filter_and_oscillator_vs_model(emu, D, n_taps):
-    W.check_filter_vs_model(factory, D, n_taps, "u8")
+    F.check_filter_vs_model(factory, F.Integer(D), n_taps, "u8")
 
 
-@pytest.mark.parametrize("fmt", [f for f in W.FORMATS if f != "u8"])
+@pytest.mark.parametrize("fmt", [f for f in F.FORMATS if f != "u8"])
 def test_sample_formats_vs_model(emu, fmt):
-    W.check_filter_vs_model(factory, 4, 64, fmt)
+    F.check_filter_vs_model(factory, K["rate"], K["n_taps"], fmt)
 
 
 def test_chunking_is_bit_identical(emu):
-    W.check_chunking(factory)
+    F.check_chunking(factory, K["rate"], K["n_taps"])
 
 
 def test_phase_over_a_long_run(emu):
-    W.check_phase_long_run(factory)
+    F.check_phase_long_run(factory, **K["long_run"])
 
 
 def test_ring_wrap(emu):
-    W.check_ring_wrap(factory)
+    F.check_ring_wrap(factory, **K["wrap"])
 
 
 def test_reset_keeps_the_configuration_and_clears_the_carry(emu):
-    W.check_reset(factory)
+    F.check_reset(factory, K["rate"], K["n_taps"], K["reset_n1"])
 
 
 def test_nothing_left_behind(emu):
@@ -45,19 +47,19 @@ def test_nothing_left_behind(emu):
     def live():
         out = (C.c_int64 * 4)(); C.CDLL(EMU_LIB).hipemu_live_counts(out); return tuple(out)
     before = live()
-    raw, taps, offsets = W.filter_case(4, 64, "u8")
+    raw, taps, offsets = F.filter_case(K["rate"], K["n_taps"], "u8")
     d = factory(n_ensembles=3, max_frames=1, want_constellation=False)
-    d.stream_open_wideband(W.RING_MIN, 4, taps, offsets, "u8")
+    d.stream_open_wideband(F.RING_MIN, 4, taps, offsets, "u8")
     d.stream_write_wideband(raw)
     d.stream_write_wideband_async(np.ascontiguousarray(raw[:64])); d.stream_commit()
-    d.stream_open_wideband(W.RING_MIN, 2, taps, W.filter_offsets(2), "s16le")          # a second open reuses or replaces, never leaks
+    d.stream_open_wideband(F.RING_MIN, 2, taps, F.Integer(2).filter_offsets(), "s16le")          # a second open reuses or replaces, never leaks
     d.close()
     assert live() == before
 
 
 def test_limits_and_state_errors(emu):
-    W.check_errors(factory)
+    F.check_errors(factory, K["rate"], K["n_taps"])
 
 
 def test_end_to_end_vs_oracle_on_the_direct_streams(emu):
-    W.check_end_to_end(factory, D=4, offsets=(-107, 0, 107))
+    F.check_end_to_end(factory, F.Integer(4), offsets=(-107, 0, 107))

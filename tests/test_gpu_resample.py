@@ -1,52 +1,54 @@
 """Device suite: the wideband front end at a rational rate (one capture at 2.048 MS/s x M / L resampled into the batch's ensembles)
 against the float64 model of tests/resample_model.py and, end to end, against the oracle on each ensemble's direct stream.
-Cases: tests/resample_cases.py."""
+Cases: tests/frontend_cases.py."""
 import pytest
 
-import resample_cases as RC
+import frontend_cases as F
 from conftest import GPU_LIB
 from welle_io_amd import capi
 
 pytestmark = pytest.mark.gpu
+
+K = F.RATIONAL                           # the kind's default shapes
 
 
 def factory(**kw):
     return capi.DabPhy(lib_path=GPU_LIB, **kw)
 
 
-@pytest.mark.parametrize("L,M,n_taps", RC.SHAPES)
+@pytest.mark.parametrize("L,M,n_taps", F.RATIONAL_SHAPES)
 def test_filter_and_oscillator_vs_model(gpu, L, M, n_taps):
-    RC.check_filter_vs_model(factory, L, M, n_taps, "u8")
+    F.check_filter_vs_model(factory, F.Rational(L, M), n_taps, "u8")
 
 
-@pytest.mark.parametrize("fmt", [f for f in RC.FORMATS if f != "u8"])
+@pytest.mark.parametrize("fmt", [f for f in F.FORMATS if f != "u8"])
 def test_sample_formats_vs_model(gpu, fmt):
-    RC.check_filter_vs_model(factory, 32, 125, 500, fmt)
+    F.check_filter_vs_model(factory, K["rate"], K["n_taps"], fmt)
 
 
 def test_chunking_is_bit_identical(gpu):
-    RC.check_chunking(factory)
+    F.check_chunking(factory, K["rate"], K["n_taps"])
 
 
 def test_phase_over_a_long_run(gpu):
-    RC.check_phase_long_run(factory)
+    F.check_phase_long_run(factory, **K["long_run"])
 
 
 def test_ring_wrap(gpu):
-    RC.check_ring_wrap(factory)
+    F.check_ring_wrap(factory, **K["wrap"])
 
 
 def test_reset_keeps_the_configuration_and_clears_the_carry(gpu):
-    RC.check_reset(factory)
+    F.check_reset(factory, K["rate"], K["n_taps"], K["reset_n1"])
 
 
 def test_limits_and_state_errors(gpu):
-    RC.check_errors(factory)
+    F.check_errors(factory, K["rate"], K["n_taps"])
 
 
 def test_end_to_end_vs_oracle_on_the_direct_streams(gpu):
-    RC.check_end_to_end(factory, L=32, Mx=125, n_taps=2000, offsets=(-107, 0, 107))
+    F.check_end_to_end(factory, F.Rational(32, 125), n_taps=2000, offsets=(-107, 0, 107))
 
 
 def test_end_to_end_at_10_ms_per_s(gpu):
-    RC.check_end_to_end(factory, L=128, Mx=625, n_taps=10000, offsets=(-107, 0, 107))
+    F.check_end_to_end(factory, F.Rational(128, 625), n_taps=10000, offsets=(-107, 0, 107))

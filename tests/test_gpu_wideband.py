@@ -1,47 +1,49 @@
 """Device suite: the wideband front end (one capture channelised into the batch's ensembles) against the float64 model of
-tests/wideband_model.py and, end to end, against the oracle on each ensemble's direct stream.  Cases: tests/wideband_cases.py."""
+tests/wideband_model.py and, end to end, against the oracle on each ensemble's direct stream.  Cases: tests/frontend_cases.py."""
 import pytest
 
-import wideband_cases as W
+import frontend_cases as F
 from conftest import GPU_LIB
 from welle_io_amd import capi
 
 pytestmark = pytest.mark.gpu
+
+K = F.INTEGER                           # the kind's default shapes
 
 
 def factory(**kw):
     return capi.DabPhy(lib_path=GPU_LIB, **kw)
 
 
-@pytest.mark.parametrize("D,n_taps", W.SHAPES)
+@pytest.mark.parametrize("D,n_taps", F.INTEGER_SHAPES)
 def test_filter_and_oscillator_vs_model(gpu, D, n_taps):
-    W.check_filter_vs_model(factory, D, n_taps, "u8")
+    F.check_filter_vs_model(factory, F.Integer(D), n_taps, "u8")
 
 
-@pytest.mark.parametrize("fmt", [f for f in W.FORMATS if f != "u8"])
+@pytest.mark.parametrize("fmt", [f for f in F.FORMATS if f != "u8"])
 def test_sample_formats_vs_model(gpu, fmt):
-    W.check_filter_vs_model(factory, 4, 64, fmt)
+    F.check_filter_vs_model(factory, K["rate"], K["n_taps"], fmt)
 
 
 def test_chunking_is_bit_identical(gpu):
-    W.check_chunking(factory)
+    F.check_chunking(factory, K["rate"], K["n_taps"])
 
 
 def test_phase_over_a_long_run(gpu):
-    W.check_phase_long_run(factory)
+    F.check_phase_long_run(factory, **K["long_run"])
 
 
 def test_ring_wrap(gpu):
-    W.check_ring_wrap(factory)
+    F.check_ring_wrap(factory, **K["wrap"])
 
 
 def test_reset_keeps_the_configuration_and_clears_the_carry(gpu):
-    W.check_reset(factory)
+    F.check_reset(factory, K["rate"], K["n_taps"], K["reset_n1"])
 
 
 def test_limits_and_state_errors(gpu):
-    W.check_errors(factory)
+    F.check_errors(factory, K["rate"], K["n_taps"])
 
 
 def test_end_to_end_vs_oracle_on_the_direct_streams(gpu):
-    W.check_end_to_end(factory, D=4, offsets=(-107, 0, 107))
+    F.check_end_to_end(factory, F.Integer(4), offsets=(-107, 0, 107))

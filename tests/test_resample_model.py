@@ -5,7 +5,7 @@ import pytest
 
 import resample_model as RM
 import wideband_model as WM
-from wideband_cases import random_taps
+from frontend_cases import random_taps
 from welle_io_amd import wideband
 
 

@@ -1,7 +1,7 @@
 // welle.io_amd/csrc/dabphy_internal.h -- what the translation units of the C ABI share: the handle (streams, events, device buffers of one
 // receiver batch), small host helpers, and the internal functions that cross files.  Not installed, not part of include/dabphy.h.
 //   dabphy_api.hip          create / destroy / options / sub-channel classes, the stateless seams (demod, Viterbi, FIC, RS) and the timing drivers
-//   dabphy_stream.hip       sample rings (bind / upload / write / raw formats / wideband capture), the synchroniser's chain and wide pass, reset
+//   dabphy_stream.hip       sample rings (bind / upload / write / raw formats), the wideband front end's open and write calls (dabphy_handle::Wideband), the synchroniser's chain and wide pass, reset
 //   dabphy_process.hip      dabphy_process: the pipelined schedules, exact batch mode (replay), the decode of one batch as named steps
 //   dabphy_fused.hip        the fused decode's host side: per-class step tables, the launch plan (build, classes, work list)
 //   dabphy_superframes.hip  Reed-Solomon seams and the DAB+ superframe filter
@@ -10,6 +10,7 @@
 //   dabphy_au.hip           the bulk access-unit drain: the pack pass behind the filter (k_au.hip), its tables and its copy to the host
 //   k_sync.hip              the synchroniser's kernels, with one header per reference function: sync_window.h (PhaseReference::findIndex:
 //                           impulse response, the three window-index methods), sync_fine.h (the fine corrector's step and its interval test; host-compilable); block_reduce.h (their work-group reduction)
+//   k_wideband.hip, k_resample.hip   the wideband front end's main kernels (integer, rational rate); capture_sample (dabphy_kernels.h) and k_capture_carry (k_ingest.hip) serve both
 //   soft_layout.h           where a code word's soft bits lie in the soft-bit ring, for kernels and host alike (dabphy_fused.hip's step tables)
 // Ownership: a device buffer (DevBuf) owns itself and is freed by its destructor; streams, events and page-locked blocks are created
 // through new_stream / new_event / pinned_alloc below and nowhere else, which register them with the handle for dabphy_destroy.
@@ -28,6 +29,8 @@
 #include <cmath>
 #include <algorithm>
 #include <chrono>
+#include <functional>
+#include <numeric>
 
 #define DABPHY_INTERNAL __attribute__((visibility("hidden")))
 
@@ -129,23 +132,21 @@ struct dabphy_handle {
     DevBuf s_raw2[2]; hipStream_t copy_stream = nullptr; hipEvent_t ev_ingest[2] = {nullptr, nullptr}; int raw_sel = 0;   // dabphy_stream_write_raw_async
     uint64_t s_enqueued = 0; int commit_slot = -1;    // samples handed to the copy stream so far; slot whose event covers the committed ones
     DevBuf s_null;                          // null symbols on request (dabphy_get_null_symbols)
-    // Wideband front end (dabphy_stream_open_wideband; k_wideband.hip): one capture at D x 2.048 MS/s channelised into the ring rows.  The
-    // open call creates every buffer -- tables, both carries, the three staging buffers at the largest write (ring * D samples) -- and
-    // a plain open or bind drops the configuration (the buffers stay with the handle, grow-only like the rest).  Carried from write to
-    // write: the carry (dabphy_reset clears it) and the absolute capture index `abs`; both follow the order the writes are QUEUED in.
+    // Wideband front end: one capture channelised into the ring rows, at D x 2.048 MS/s (INTEGER: dabphy_stream_open_wideband,
+    // k_wideband.hip) or at 2.048 MS/s x M / L (RATIONAL: dabphy_stream_open_resampled, k_resample.hip).  The open call creates every
+    // buffer -- its kind's tables, both carries, the three staging buffers at the largest write -- and a plain open or bind drops the
+    // configuration (OFF; the buffers stay with the handle, grow-only like the rest).  Both kinds share the write calls and what they
+    // carry: the carry (dabphy_reset clears it) and the capture index `abs`, in the order the writes are QUEUED in.  Each kind owns its
+    // geometry, its tables and its last synchronous write as it was launched (`last`, with last_valid: dabphy_time_wideband runs it again).
     struct Wideband {
-        bool on = false;
-        uint32_t D = 0, n_taps = 0, e_pad = 0; int32_t format = 0;
-        DevBuf ctaps, osc, om, carry[2]; int carry_sel = 0;      // carry[carry_sel] lies in front of the next write
-        uint64_t abs = 0;                                        // capture samples written since the open / reset
-        WidebandArgs last{}; bool last_valid = false;            // the last synchronous write as it was launched (dabphy_time_wideband runs it again)
-        // ... or at 2.048 MS/s x M / L (dabphy_stream_open_resampled; k_resample.hip): the same two write calls, carries and staging
-        // buffers.  Exact integers carried from write to write: `abs` = N, and frac = (N L) mod M -- the stream holds (N L - frac) / M
-        // outputs, and M - 1 - frac says where the next one's newest sample lies and which phase it has
-        bool rational = false;
-        uint32_t L = 0, M = 0, J = 0; uint64_t frac = 0, stage_samples = 0;
-        DevBuf rs_taps, rs_osc_lo;                               // [J + RS_TAP_STEP][L]; [n_ens][RS_OSC_LO] (`osc` holds [n_ens][n_hi]; ctaps and om are the integer path's)
-        ResampleArgs rs_last{};
+        enum Kind { OFF, INTEGER, RATIONAL } kind = OFF;
+        int32_t format = 0;
+        DevBuf carry[2]; int carry_sel = 0; uint32_t carry_len = 0;   // carry[carry_sel]: the carry_len samples in front of the next write
+        uint64_t abs = 0; bool last_valid = false;               // abs: capture samples written since the open / reset, N
+        struct Integer { uint32_t D = 0, n_taps = 0, e_pad = 0; DevBuf ctaps, osc, om; WidebandArgs last{}; } integer;      // (tables: WidebandArgs has their shapes)
+        // exact integers beside N: frac = (N L) mod M -- the stream holds (N L - frac) / M outputs, and M - 1 - frac says where the next
+        // one's newest sample lies and which phase it has; stage_samples: no write is as long as this.  (Tables: ResampleArgs)
+        struct Rational { uint32_t L = 0, M = 0, J = 0; uint64_t frac = 0, stage_samples = 0; DevBuf taps, osc_hi, osc_lo; ResampleArgs last{}; } rational;
     } wb;
     // bulk MSC drain (dabphy_msc_drain_begin / _wait): the class outputs leave on a stream of their own while the next batch starts
     hipStream_t drain_stream = nullptr; hipEvent_t ev_drain_done = nullptr, ev_drain_staged = nullptr; bool drain_pending = false; DevBuf drain_stage;
@@ -321,6 +322,13 @@ template <typename T> int upload_const(dabphy_handle* h, T** dst, const std::vec
     int r;
     if ((r = device_block(h, dst, src.size()))) return r;
     HIPCHK(h, hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+// ... or a table in grow-only scratch, copied on the handle's stream: `src` stays as it is until that stream has been waited for
+template <typename T> int upload_table(dabphy_handle* h, DevBuf& b, const std::vector<T>& src)
+{
+    if (int r = ensure(h, b, src.size() * sizeof(T))) return r;
+    HIPCHK(h, hipMemcpyAsync(b.p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
     return 0;
 }
 

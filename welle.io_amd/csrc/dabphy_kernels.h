@@ -281,7 +281,7 @@ struct IngestArgs {
 };
 void launch_ingest(const IngestArgs& a, int n_ens, hipStream_t s);
 // Sample i of a raw stream as cf32: the arithmetic of CRAWFile::convertSamples (k_ingest.hip's header has the formats), stated once for
-// k_ingest and the wideband channeliser.  format = DABPHY_FMT_U8 ... _S16BE
+// k_ingest and the wideband front ends (capture_sample below).  format = DABPHY_FMT_U8 ... _S16BE
 __device__ __forceinline__ cf32 ingest_sample(const uint8_t* __restrict__ src, uint64_t i, int format)
 {
     cf32 v;
@@ -300,6 +300,20 @@ __device__ __forceinline__ cf32 ingest_sample(const uint8_t* __restrict__ src, u
     }
     return v;
 }
+constexpr size_t sample_bytes(int format) { return format == 0 ? 8 : (format == 1 || format == 2) ? 2 : 4; }      // of a raw stream; cf32 = 0
+// The capture of one write to a wideband stream as both front ends and the carry kernel read it: the call's n samples of `format`, the
+// carry_len converted samples in front of them (the end of the stream so far; zeros at its start), zeros behind
+struct CaptureSrc { const uint8_t* raw; int format; uint64_t n; const cf32* carry_in; uint32_t carry_len; };
+__device__ __forceinline__ cf32 capture_sample(const CaptureSrc& c, int64_t gi)      // gi: index in the call
+{
+    cf32 v; v.re = 0.0f; v.im = 0.0f;
+    if (gi >= 0) { if ((uint64_t)gi < c.n) v = c.format == 0 ? reinterpret_cast<const cf32*>(c.raw)[gi] : ingest_sample(c.raw, (uint64_t)gi, c.format); }
+    else if (gi >= -(int64_t)c.carry_len) v = c.carry_in[(int64_t)c.carry_len + gi];
+    return v;
+}
+struct RingDst { cf32* iq; size_t iq_stride; uint64_t ring, w; };      // ... and where its outputs go: output 0 to ring position w of every ensemble's row
+// The carry behind a call (k_ingest.hip), when it has a length: the last carry_len samples of (carry_in, the call's samples), into the OTHER buffer
+void launch_capture_carry(const CaptureSrc& c, cf32* carry_out, hipStream_t s);
 
 // Wideband channeliser (k_wideband.hip): one capture at D x 2.048 MS/s -> the ring rows of the handle's ensembles.
 //   y_e[m] = osc[(om_e * a) mod P] * sum_k ctaps[k][e] * c(x[a - k]),   a = m D + D - 1 (absolute capture index), P = 128 D
@@ -312,10 +326,9 @@ constexpr int WB_TILE_SMALL = 2560, WB_TILE_MID = 4864, WB_TILE_LARGE = 7168;   
 // taps the kernel FETCHES for a filter of n_taps: whole steps, and one step ahead -- rows of the tap table (zeros from n_taps on) and samples of halo
 constexpr uint32_t wideband_reach(uint32_t n_taps) { return (n_taps + WB_TAP_STEP - 1) / WB_TAP_STEP * WB_TAP_STEP + WB_TAP_STEP; }
 struct WidebandArgs {
-    const uint8_t* raw; int format; uint64_t n, n_out;    // the call's capture: n samples (c() = ingest_sample, or cf32 as it is), n_out = n / D outputs
-    const cf32* carry_in; cf32* carry_out;                // the n_taps - 1 converted samples in front of the call / behind it (two buffers, swapped by the host)
+    CaptureSrc src; uint64_t n_out; cf32* carry_out;      // the call's capture (c() = capture_sample; the carry holds n_taps - 1 samples), n_out = n / D outputs, the carry behind it
     const cf32* ctaps; const cf32* osc; const uint32_t* om;   // [wideband_reach(n_taps)][e_pad] (zeros from row n_taps on), [P], [n_ens] offset mod P
-    cf32* iq; size_t iq_stride; uint64_t ring, w;         // output 0 goes to ring position w of every row
+    RingDst dst;
     uint32_t D, n_taps, P, n_ens, e_pad, abs_mod;         // abs_mod: absolute index of the call's first capture sample, mod P
     uint32_t T, halo, W;                                  // outputs per tile (512, 256 or 128: the 256 threads are 512 / T groups of T / 2 lanes), samples in front of a tile's first (a multiple of D >= wideband_reach(n_taps) - 1), tile row pitch
 };
@@ -336,10 +349,9 @@ constexpr int RS_OSC_LO = 256;                                       // radix of
 constexpr int RS_MIX_STEP = 4;                                       // span entries a thread converts and mixes per turn, their loads in flight together
 constexpr int RS_TILE_SMALL = 2560, RS_TILE_MID = 4864, RS_TILE_LARGE = 8192;   // samples of LDS the kernel's builds hold (8, 4, 2 work-groups per compute unit)
 struct ResampleArgs {
-    const uint8_t* raw; int format; uint64_t n, n_out;    // the call's capture: n samples, n_out outputs (may be 0: only the carry moves)
-    const cf32* carry_in; cf32* carry_out;                // the J - 1 converted samples in front of the call / behind it (two buffers, swapped by the host)
+    CaptureSrc src; uint64_t n_out; cf32* carry_out;      // the call's capture (the carry holds J - 1 samples), n_out outputs (may be 0: only the carry moves), the carry behind it
     const float* taps; const cf32* osc_hi; const cf32* osc_lo; uint32_t n_hi;   // [J + RS_TAP_STEP][L], [n_ens][n_hi] with n_hi = ceil(P / RS_OSC_LO), [n_ens][RS_OSC_LO]
-    cf32* iq; size_t iq_stride; uint64_t ring, w;         // output 0 of the call goes to ring position w of every row
+    RingDst dst;
     uint32_t L, M, J, P, n_ens;                           // J: taps per phase as the kernel adds them, a multiple of RS_TAP_STEP
     uint32_t a0, r0, abs_mod;                             // the call's first output: index in the call of its newest sample, its phase; absolute index of the call's sample 0, mod P
     uint32_t T, G, Q, W, S;                               // outputs per tile = threads per work-group; ensembles per pass; span layout: entry s at (s mod Q) W + s div Q; entries per span

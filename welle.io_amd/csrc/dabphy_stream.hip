@@ -2,6 +2,8 @@
 // (split from dabphy_api.hip in round 3; dabphy_internal.h has the map of the translation units)
 #include "dabphy_internal.h"
 
+using Wideband = dabphy_handle::Wideband;
+
 extern "C" {
 
 // =================================================================================== streaming receiver
@@ -132,7 +134,7 @@ static int wideband_clear(dabphy_handle* h)
 {
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));          // writes still queued there read and write the carry
     for (DevBuf& c : h->wb.carry) HIPCHK(h, hipMemsetAsync(c.p, 0, c.cap, h->stream));
-    h->wb.abs = 0; h->wb.frac = 0; h->wb.carry_sel = 0; h->wb.last_valid = false;
+    h->wb.abs = 0; h->wb.rational.frac = 0; h->wb.carry_sel = 0; h->wb.last_valid = false;
     return DABPHY_OK;
 }
 
@@ -154,7 +156,7 @@ int dabphy_reset(dabphy_handle* h)
     // ... and the frame count starts over: every selected sub-channel's time de-interleaver fills again from the first CIF decoded
     for (auto& c : h->classes) { for (MscPair& p : c.pairs) p.cif0 = -1; int r2 = upload_pairs(h, c); if (r2) return r2; }
     h->tii_ran = false;
-    if (h->wb.on && (r = wideband_clear(h))) return r;
+    if (h->wb.kind != Wideband::OFF && (r = wideband_clear(h))) return r;
     return sync(h);
 }
 
@@ -166,7 +168,7 @@ int dabphy_stream_bind_device(dabphy_handle* h, const void* d_iq, uint64_t ring_
     h->s_iq = reinterpret_cast<const cf32*>(d_iq); h->s_ring = ring_samples; h->s_stride = stride_samples;
     h->s_valid = n_valid; h->s_enqueued = 0; h->commit_slot = -1; h->s_loop = loop;
     h->s_bounded = false;                                         // the caller's cf32 samples: no bound known
-    h->wb.on = false; h->wb.last_valid = false;                   // a stream bound or opened any other way is no wideband stream
+    h->wb.kind = Wideband::OFF; h->wb.last_valid = false;         // a stream bound or opened any other way is no wideband stream
     return dabphy_reset(h);
 }
 
@@ -195,21 +197,60 @@ int dabphy_stream_open(dabphy_handle* h, uint64_t ring_samples)
     return r;
 }
 
+// ---- what the write and read calls below share, each stated once.  The write calls take the handle's own ring, not a caller's buffer
+static bool owns_ring(const dabphy_handle* h) { return h->s_iq_own.p && h->s_iq == h->s_iq_own.as<cf32>(); }
+// a synchronous write waits for the chain that may be running ahead and, on a wideband stream, for the asynchronous writes' carry
+static int writer_wait(dabphy_handle* h, bool copies_too)
+{
+    HIPCHK(h, hipStreamSynchronize(h->sync_stream));
+    if (copies_too) HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+    return DABPHY_OK;
+}
+// An asynchronous write takes the staging slot of the call before last -- free, and that call's host buffer with it, once its conversion
+// has run -- and copies `data` there on the copy stream; behind its launches (n_appended samples) it records when the slot is free again
+static int stage_acquire(dabphy_handle* h, const void* data, size_t bytes, int* slot)
+{
+    if (h->s_enqueued < h->s_valid) h->s_enqueued = h->s_valid;            // synchronous writes in between
+    *slot = h->raw_sel; h->raw_sel ^= 1;
+    HIPCHK(h, hipEventSynchronize(h->ev_ingest[*slot]));
+    const int r = ensure(h, h->s_raw2[*slot], bytes);                       // (a wideband stream's open call has made it large enough)
+    if (!r) HIPCHK(h, hipMemcpyAsync(h->s_raw2[*slot].p, data, bytes, hipMemcpyHostToDevice, h->copy_stream));
+    return r;
+}
+static int stage_release(dabphy_handle* h, int slot, uint64_t n_appended) { HIPCHK(h, hipEventRecord(h->ev_ingest[slot], h->copy_stream)); h->s_enqueued += n_appended; return DABPHY_OK; }
+// n ring samples from pos on: up to the ring's end, then from its start.  Piece i: at[i] into a row, n[i] long (or 0), done[i] into the span
+struct RingSpan { uint64_t at[2], n[2], done[2]; };
+static RingSpan ring_span(const dabphy_handle* h, uint64_t pos, uint64_t n)
+{
+    const uint64_t w = pos % h->s_ring, first = std::min<uint64_t>(n, h->s_ring - w);
+    return RingSpan{{w, 0}, {first, n - first}, {0, first}};
+}
+// the plain raw writers: their checks, and the conversion of n samples per ensemble staged at `raw` to ring position `written` on
+static int raw_write_check(const dabphy_handle* h, const void* data, uint64_t n_samples, int32_t format)
+{
+    if (!h || !data || !owns_ring(h) || n_samples == 0 || n_samples > h->s_ring || format < DABPHY_FMT_U8 || format > DABPHY_FMT_S16BE) return DABPHY_ERR_INVALID;
+    return h->wb.kind != Wideband::OFF ? DABPHY_ERR_STATE : DABPHY_OK;     // a wideband stream takes the capture (dabphy_stream_write_wideband)
+}
+static void ingest(const dabphy_handle* h, const DevBuf& raw, uint64_t n_samples, int32_t format, uint64_t written, hipStream_t s)
+{
+    IngestArgs a{};
+    a.raw = raw.as<uint8_t>(); a.raw_stride = n_samples * sample_bytes(format); a.iq = h->s_iq_own.as<cf32>(); a.iq_stride = h->s_stride;
+    a.ring = h->s_ring; a.w = written % h->s_ring; a.n = n_samples; a.format = format;
+    launch_ingest(a, (int)h->cfg.n_ensembles, s);
+}
+
 int dabphy_stream_write(dabphy_handle* h, const float* iq, uint64_t n_samples)
 {
     DeviceBind dev_(h);
-    if (!h || !iq || !h->s_iq_own.p || h->s_iq != h->s_iq_own.as<cf32>() || n_samples == 0 || n_samples > h->s_ring) return DABPHY_ERR_INVALID;
-    if (h->wb.on) return DABPHY_ERR_STATE;                        // a wideband stream takes the capture (dabphy_stream_write_wideband)
+    if (!h || !iq || !owns_ring(h) || n_samples == 0 || n_samples > h->s_ring) return DABPHY_ERR_INVALID;
+    if (h->wb.kind != Wideband::OFF) return DABPHY_ERR_STATE;     // a wideband stream takes the capture (dabphy_stream_write_wideband)
     h->s_bounded = false;                                         // cf32 from the caller: any magnitude
-    // the chain that may be running ahead must not race with the copy
-    HIPCHK(h, hipStreamSynchronize(h->sync_stream));
-    const uint64_t w = h->s_valid % h->s_ring;
-    const uint64_t first = std::min<uint64_t>(n_samples, h->s_ring - w);
+    if (int r = writer_wait(h, false)) return r;
+    const RingSpan sp = ring_span(h, h->s_valid, n_samples);
     for (uint32_t b = 0; b < h->cfg.n_ensembles; b++) {
         cf32* dst = h->s_iq_own.as<cf32>() + (size_t)b * h->s_stride;
         const cf32* src = reinterpret_cast<const cf32*>(iq) + (size_t)b * n_samples;
-        HIPCHK(h, hipMemcpyAsync(dst + w, src, first * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
-        if (first < n_samples) HIPCHK(h, hipMemcpyAsync(dst, src + first, (n_samples - first) * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
+        for (int i = 0; i < 2; i++) if (sp.n[i]) HIPCHK(h, hipMemcpyAsync(dst + sp.at[i], src + sp.done[i], sp.n[i] * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
     }
     h->s_valid += n_samples;
     return sync(h);
@@ -219,19 +260,12 @@ int dabphy_stream_write_raw(dabphy_handle* h, const void* data, uint64_t n_sampl
 {
     DeviceBind dev_(h);
     if (format == DABPHY_FMT_CF32) return dabphy_stream_write(h, reinterpret_cast<const float*>(data), n_samples);
-    if (!h || !data || !h->s_iq_own.p || h->s_iq != h->s_iq_own.as<cf32>() || n_samples == 0 || n_samples > h->s_ring ||
-        format < DABPHY_FMT_U8 || format > DABPHY_FMT_S16BE) return DABPHY_ERR_INVALID;
-    if (h->wb.on) return DABPHY_ERR_STATE;
-    const size_t bps = (format == DABPHY_FMT_U8 || format == DABPHY_FMT_S8) ? 2 : 4;
-    const uint32_t B = h->cfg.n_ensembles;
     int r;
-    if ((r = ensure(h, h->s_raw, (size_t)B * n_samples * bps))) return r;
-    HIPCHK(h, hipStreamSynchronize(h->sync_stream));           // the chain that may be running ahead must not race with the write
-    HIPCHK(h, hipMemcpyAsync(h->s_raw.p, data, (size_t)B * n_samples * bps, hipMemcpyHostToDevice, h->stream));
-    IngestArgs a{};
-    a.raw = h->s_raw.as<uint8_t>(); a.raw_stride = n_samples * bps; a.iq = h->s_iq_own.as<cf32>(); a.iq_stride = h->s_stride;
-    a.ring = h->s_ring; a.w = h->s_valid % h->s_ring; a.n = n_samples; a.format = format;
-    launch_ingest(a, (int)B, h->stream);
+    if ((r = raw_write_check(h, data, n_samples, format))) return r;
+    const size_t bytes = (size_t)h->cfg.n_ensembles * n_samples * sample_bytes(format);
+    if ((r = ensure(h, h->s_raw, bytes)) || (r = writer_wait(h, false))) return r;
+    HIPCHK(h, hipMemcpyAsync(h->s_raw.p, data, bytes, hipMemcpyHostToDevice, h->stream));
+    ingest(h, h->s_raw, n_samples, format, h->s_valid, h->stream);
     h->s_valid += n_samples;
     return sync(h);
 }
@@ -242,38 +276,36 @@ int dabphy_stream_read(dabphy_handle* h, uint32_t ensemble, uint64_t pos, uint64
     if (!h || !out || !h->s_iq || ensemble >= h->cfg.n_ensembles || n_samples == 0 || n_samples > h->s_ring) return DABPHY_ERR_INVALID;
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
     const cf32* src = h->s_iq + (size_t)ensemble * h->s_stride;
-    const uint64_t w = pos % h->s_ring, first = std::min<uint64_t>(n_samples, h->s_ring - w);
-    HIPCHK(h, hipMemcpyAsync(out, src + w, first * sizeof(cf32), hipMemcpyDeviceToHost, h->stream));
-    if (first < n_samples) HIPCHK(h, hipMemcpyAsync(out + 2 * first, src, (n_samples - first) * sizeof(cf32), hipMemcpyDeviceToHost, h->stream));
+    const RingSpan sp = ring_span(h, pos, n_samples);
+    for (int i = 0; i < 2; i++) if (sp.n[i]) HIPCHK(h, hipMemcpyAsync(out + 2 * sp.done[i], src + sp.at[i], sp.n[i] * sizeof(cf32), hipMemcpyDeviceToHost, h->stream));
     return sync(h);
 }
 
 int dabphy_stream_write_raw_async(dabphy_handle* h, const void* data, uint64_t n_samples, int32_t format)
 {
     DeviceBind dev_(h);
-    if (!h || !data || !h->s_iq_own.p || h->s_iq != h->s_iq_own.as<cf32>() || n_samples == 0 || n_samples > h->s_ring ||
-        format < DABPHY_FMT_U8 || format > DABPHY_FMT_S16BE) return DABPHY_ERR_INVALID;
-    if (h->wb.on) return DABPHY_ERR_STATE;
-    const size_t bps = (format == DABPHY_FMT_U8 || format == DABPHY_FMT_S8) ? 2 : 4;
-    const uint32_t B = h->cfg.n_ensembles;
-    if (h->s_enqueued < h->s_valid) h->s_enqueued = h->s_valid;            // synchronous writes in between
-    const int slot = h->raw_sel; h->raw_sel ^= 1;
-    // the staging slot (and with it the host buffer of the call before last) is free once its previous conversion has run
-    HIPCHK(h, hipEventSynchronize(h->ev_ingest[slot]));
-    int r;
-    if ((r = ensure(h, h->s_raw2[slot], (size_t)B * n_samples * bps))) return r;
-    HIPCHK(h, hipMemcpyAsync(h->s_raw2[slot].p, data, (size_t)B * n_samples * bps, hipMemcpyHostToDevice, h->copy_stream));
-    IngestArgs a{};
-    a.raw = h->s_raw2[slot].as<uint8_t>(); a.raw_stride = n_samples * bps; a.iq = h->s_iq_own.as<cf32>(); a.iq_stride = h->s_stride;
-    a.ring = h->s_ring; a.w = h->s_enqueued % h->s_ring; a.n = n_samples; a.format = format;
-    launch_ingest(a, (int)B, h->copy_stream);
-    HIPCHK(h, hipEventRecord(h->ev_ingest[slot], h->copy_stream));
-    h->s_enqueued += n_samples;
-    return DABPHY_OK;
+    int r, slot;
+    if ((r = raw_write_check(h, data, n_samples, format)) ||
+        (r = stage_acquire(h, data, (size_t)h->cfg.n_ensembles * n_samples * sample_bytes(format), &slot))) return r;
+    ingest(h, h->s_raw2[slot], n_samples, format, h->s_enqueued, h->copy_stream);
+    return stage_release(h, slot, n_samples);
 }
 
-// ---- wideband front end: one capture, channelised into every ensemble's ring row (k_wideband.hip)
-static size_t wideband_bps(int32_t format) { return format == DABPHY_FMT_CF32 ? 8 : (format == DABPHY_FMT_U8 || format == DABPHY_FMT_S8) ? 2 : 4; }
+// ---- wideband front end: one capture, channelised into every ensemble's ring row (k_wideband.hip; at a rational rate k_resample.hip)
+// What the two open calls do once their own limits and geometry have passed (a refused open leaves the stream there was): the ring
+// and the reset, which drop an earlier configuration (the kind is OFF until all is in place); both carries and the three staging buffers
+// at stage_samples, more than the largest write; the kind's geometry and tables (upload_tables); the carried state at a capture's start
+static int wideband_open(dabphy_handle* h, uint64_t ring_samples, Wideband::Kind kind, int32_t format, uint32_t carry_len, uint64_t stage_samples, const std::function<int()>& upload_tables)
+{
+    int r;
+    if ((r = dabphy_stream_open(h, ring_samples))) return r;
+    const size_t carry_bytes = (size_t)std::max<uint32_t>(carry_len, 1) * sizeof(cf32), stage = (size_t)stage_samples * sample_bytes(format);
+    if ((r = ensure(h, h->wb.carry[0], carry_bytes)) || (r = ensure(h, h->wb.carry[1], carry_bytes)) ||
+        (r = ensure(h, h->s_raw, stage)) || (r = ensure(h, h->s_raw2[0], stage)) || (r = ensure(h, h->s_raw2[1], stage)) || (r = upload_tables())) return r;
+    h->wb.kind = kind; h->wb.format = format; h->wb.carry_len = carry_len;
+    h->s_bounded = false;                                         // a FIR's output: no bound known (the sLevel bracket of sync_args relies on one)
+    return (r = wideband_clear(h)) ? r : sync(h);                 // (the caller's host tables go out of scope)
+}
 
 int dabphy_stream_open_wideband(dabphy_handle* h, uint64_t ring_samples, const dabphy_wideband_config* cfg)
 {
@@ -284,8 +316,6 @@ int dabphy_stream_open_wideband(dabphy_handle* h, uint64_t ring_samples, const d
     for (uint32_t e = 0; e < B; e++) if (cfg->offset_16khz[e] > 64 * (int32_t)D || cfg->offset_16khz[e] < -64 * (int32_t)D) return DABPHY_ERR_INVALID;
     WidebandArgs geo{}; geo.D = D; geo.n_taps = n_taps;
     if (!wideband_geometry(geo)) return DABPHY_ERR_INVALID;
-    int r;
-    if ((r = dabphy_stream_open(h, ring_samples))) return r;     // the ring and the reset; drops an earlier configuration
     // tables, in double precision, rounded once: the oscillator over its period, every ensemble's offset mod P, its taps turned by +theta k
     const uint32_t P = 128 * D, e_pad = (B + WB_ENS_STEP - 1) / WB_ENS_STEP * WB_ENS_STEP;
     const double two_pi = 6.283185307179586476925286766559;
@@ -299,37 +329,26 @@ int dabphy_stream_open_wideband(dabphy_handle* h, uint64_t ring_samples, const d
             ctaps[(size_t)k * e_pad + e].re = (float)(t * cos(a)); ctaps[(size_t)k * e_pad + e].im = (float)(t * sin(a));
         }
     }
-    const size_t carry_bytes = (size_t)std::max<uint32_t>(n_taps - 1, 1) * sizeof(cf32), stage = (size_t)ring_samples * D * wideband_bps(cfg->format);
-    if ((r = ensure(h, h->wb.osc, osc.size() * sizeof(cf32))) || (r = ensure(h, h->wb.ctaps, ctaps.size() * sizeof(cf32))) || (r = ensure(h, h->wb.om, om.size() * sizeof(uint32_t))) ||
-        (r = ensure(h, h->wb.carry[0], carry_bytes)) || (r = ensure(h, h->wb.carry[1], carry_bytes)) ||
-        (r = ensure(h, h->s_raw, stage)) || (r = ensure(h, h->s_raw2[0], stage)) || (r = ensure(h, h->s_raw2[1], stage))) return r;
-    HIPCHK(h, hipMemcpyAsync(h->wb.osc.p, osc.data(), osc.size() * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->wb.ctaps.p, ctaps.data(), ctaps.size() * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->wb.om.p, om.data(), om.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    h->wb.D = D; h->wb.n_taps = n_taps; h->wb.e_pad = e_pad; h->wb.format = cfg->format;
-    h->wb.on = true; h->wb.rational = false;
-    h->s_bounded = false;                                         // a FIR's output: no bound known (the sLevel bracket of sync_args relies on one)
-    if ((r = wideband_clear(h))) return r;
-    return sync(h);                                               // (the host tables go out of scope)
+    // the largest write fills the ring: ring x D samples
+    return wideband_open(h, ring_samples, Wideband::INTEGER, cfg->format, n_taps - 1, ring_samples * D, [&]() -> int {
+        Wideband::Integer& w = h->wb.integer; w.D = D; w.n_taps = n_taps; w.e_pad = e_pad;
+        int r; return (r = upload_table(h, w.osc, osc)) || (r = upload_table(h, w.ctaps, ctaps)) ? r : upload_table(h, w.om, om);
+    });
 }
 
-// ---- ... at 2.048 MS/s x M / L (k_resample.hip)
-static uint32_t gcd_u32(uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; }
-
+// ---- ... at 2.048 MS/s x M / L
 int dabphy_stream_open_resampled(dabphy_handle* h, uint64_t ring_samples, const dabphy_resampler_config* cfg)
 {
     DeviceBind dev_(h);
     if (!h || !cfg || cfg->struct_size != sizeof(dabphy_resampler_config) || !cfg->taps || !cfg->offset_16khz) return DABPHY_ERR_INVALID;
     const uint32_t L = cfg->interpolation, M = cfg->decimation, n_taps = cfg->n_taps, B = h->cfg.n_ensembles;
-    if (L < 1 || L > (uint32_t)RS_MAX_L || M < 1 || M > (uint32_t)RS_MAX_M || M < L || M > (uint32_t)RS_MAX_RATIO * L || gcd_u32(L, M) != 1 ||
+    if (L < 1 || L > (uint32_t)RS_MAX_L || M < 1 || M > (uint32_t)RS_MAX_M || M < L || M > (uint32_t)RS_MAX_RATIO * L || std::gcd(L, M) != 1 ||
         n_taps < 1 || n_taps > (uint32_t)RS_MAX_TAPS_PER_PHASE * L || cfg->format < DABPHY_FMT_CF32 || cfg->format > DABPHY_FMT_S16BE) return DABPHY_ERR_INVALID;
     for (uint32_t e = 0; e < B; e++) if (std::abs((int64_t)cfg->offset_16khz[e]) * (int64_t)L > 64 * (int64_t)M) return DABPHY_ERR_INVALID;
     // taps per phase as the kernel adds them: whole fetch steps (zero taps behind a phase's last)
     const uint32_t J = ((n_taps + L - 1) / L + RS_TAP_STEP - 1) / RS_TAP_STEP * RS_TAP_STEP;
     ResampleArgs geo{}; geo.L = L; geo.M = M; geo.J = J;
     if (!resample_geometry(geo)) return DABPHY_ERR_INVALID;
-    int r;
-    if ((r = dabphy_stream_open(h, ring_samples))) return r;     // the ring and the reset; drops an earlier configuration
     // tables, in double precision, rounded once: every ensemble's oscillator at the multiples of RS_OSC_LO and at the RS_OSC_LO indices below
     // one, each from the exact phase (offset L i) mod P -- the product exceeds 2^32; the prototype
     const uint32_t P = 128 * M;
@@ -346,76 +365,71 @@ int dabphy_stream_open_resampled(dabphy_handle* h, uint64_t ring_samples, const 
     for (uint32_t k = 0; k < n_taps; k++) taps[k] = cfg->taps[k];
     // the largest write the ring takes: fewer than (ring + 1) M / L samples
     const uint64_t stage_samples = (ring_samples + 1) * M / L + 1;
-    const size_t carry_bytes = (size_t)(J - 1) * sizeof(cf32), stage = (size_t)stage_samples * wideband_bps(cfg->format);
-    if ((r = ensure(h, h->wb.osc, osc_hi.size() * sizeof(cf32))) || (r = ensure(h, h->wb.rs_taps, taps.size() * sizeof(float))) || (r = ensure(h, h->wb.rs_osc_lo, osc_lo.size() * sizeof(cf32))) ||
-        (r = ensure(h, h->wb.carry[0], carry_bytes)) || (r = ensure(h, h->wb.carry[1], carry_bytes)) ||
-        (r = ensure(h, h->s_raw, stage)) || (r = ensure(h, h->s_raw2[0], stage)) || (r = ensure(h, h->s_raw2[1], stage))) return r;
-    HIPCHK(h, hipMemcpyAsync(h->wb.osc.p, osc_hi.data(), osc_hi.size() * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->wb.rs_taps.p, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->wb.rs_osc_lo.p, osc_lo.data(), osc_lo.size() * sizeof(cf32), hipMemcpyHostToDevice, h->stream));
-    h->wb.L = L; h->wb.M = M; h->wb.J = J; h->wb.n_taps = n_taps; h->wb.format = cfg->format; h->wb.stage_samples = stage_samples;
-    h->wb.on = true; h->wb.rational = true;
-    h->s_bounded = false;                                         // a FIR's output: no bound known
-    if ((r = wideband_clear(h))) return r;
-    return sync(h);                                               // (the host tables go out of scope)
+    return wideband_open(h, ring_samples, Wideband::RATIONAL, cfg->format, J - 1, stage_samples, [&]() -> int {
+        Wideband::Rational& w = h->wb.rational; w.L = L; w.M = M; w.J = J; w.stage_samples = stage_samples;
+        int r; return (r = upload_table(h, w.osc_hi, osc_hi)) || (r = upload_table(h, w.taps, taps)) ? r : upload_table(h, w.osc_lo, osc_lo);
+    });
 }
 
 // outputs a write of n capture samples appends to a resampled stream: floor((N + n) L / M) - floor(N L / M), from frac = (N L) mod M
-static uint64_t resample_outputs(const dabphy_handle* h, uint64_t n) { return (h->wb.frac + n * h->wb.L) / h->wb.M; }
-
-// the launch of one write to a resampled stream, as wideband_args below
+static uint64_t resample_outputs(const dabphy_handle* h, uint64_t n) { return (h->wb.rational.frac + n * h->wb.rational.L) / h->wb.rational.M; }
+// Source and destination of one write's launch, for either kind: n capture samples staged at `raw` behind the carry, outputs from ring
+// position `written` on.  The write is then counted: the capture index moves on and the carries swap (when there is one to write)
+static void wideband_ends(dabphy_handle* h, const void* raw, uint64_t n, uint64_t written, CaptureSrc& src, cf32*& carry_out, RingDst& dst)
+{
+    Wideband& wb = h->wb;
+    src = CaptureSrc{reinterpret_cast<const uint8_t*>(raw), wb.format, n, wb.carry[wb.carry_sel].as<cf32>(), wb.carry_len};
+    carry_out = wb.carry[wb.carry_sel ^ 1].as<cf32>();
+    dst = RingDst{h->s_iq_own.as<cf32>(), h->s_stride, h->s_ring, written % h->s_ring};
+    wb.abs += n; if (wb.carry_len) wb.carry_sel ^= 1;
+}
 static ResampleArgs resample_args(dabphy_handle* h, const void* raw, uint64_t n, uint64_t written)
 {
+    Wideband::Rational& w = h->wb.rational;
     ResampleArgs a{};
-    a.L = h->wb.L; a.M = h->wb.M; a.J = h->wb.J; resample_geometry(a);
-    a.raw = reinterpret_cast<const uint8_t*>(raw); a.format = h->wb.format; a.n = n; a.n_out = resample_outputs(h, n);
-    a.carry_in = h->wb.carry[h->wb.carry_sel].as<cf32>(); a.carry_out = h->wb.carry[h->wb.carry_sel ^ 1].as<cf32>();
-    a.taps = h->wb.rs_taps.as<float>(); a.osc_hi = h->wb.osc.as<cf32>(); a.osc_lo = h->wb.rs_osc_lo.as<cf32>();
-    a.iq = h->s_iq_own.as<cf32>(); a.iq_stride = h->s_stride; a.ring = h->s_ring; a.w = written % h->s_ring;
-    a.P = 128 * h->wb.M; a.n_hi = (a.P + RS_OSC_LO - 1) / RS_OSC_LO; a.n_ens = h->cfg.n_ensembles; a.abs_mod = (uint32_t)(h->wb.abs % a.P);
+    a.L = w.L; a.M = w.M; a.J = w.J; resample_geometry(a); a.n_out = resample_outputs(h, n);
+    a.taps = w.taps.as<float>(); a.osc_hi = w.osc_hi.as<cf32>(); a.osc_lo = w.osc_lo.as<cf32>();
+    a.P = 128 * w.M; a.n_hi = (a.P + RS_OSC_LO - 1) / RS_OSC_LO; a.n_ens = h->cfg.n_ensembles; a.abs_mod = (uint32_t)(h->wb.abs % a.P);
     // the next output m = (N L - frac) / M: m M + M - 1 = N L + (M - 1 - frac), so its newest sample is N + (M - 1 - frac) div L
-    const uint64_t ahead = h->wb.M - 1 - h->wb.frac;
-    a.a0 = (uint32_t)(ahead / h->wb.L); a.r0 = (uint32_t)(ahead % h->wb.L);
-    h->wb.abs += n; h->wb.frac = (h->wb.frac + n * h->wb.L) % h->wb.M; h->wb.carry_sel ^= 1;
+    const uint64_t ahead = w.M - 1 - w.frac;
+    a.a0 = (uint32_t)(ahead / w.L); a.r0 = (uint32_t)(ahead % w.L);
+    w.frac = (w.frac + n * w.L) % w.M;
+    wideband_ends(h, raw, n, written, a.src, a.carry_out, a.dst);
     return a;
 }
-
-// the launch of one write: n capture samples staged at `raw`, outputs from ring position `written` on
 static WidebandArgs wideband_args(dabphy_handle* h, const void* raw, uint64_t n, uint64_t written)
 {
+    const Wideband::Integer& w = h->wb.integer;
     WidebandArgs a{};
-    a.D = h->wb.D; a.n_taps = h->wb.n_taps; wideband_geometry(a);
-    a.raw = reinterpret_cast<const uint8_t*>(raw); a.format = h->wb.format; a.n = n; a.n_out = n / h->wb.D;
-    a.carry_in = h->wb.carry[h->wb.carry_sel].as<cf32>(); a.carry_out = h->wb.carry[h->wb.carry_sel ^ 1].as<cf32>();
-    a.ctaps = h->wb.ctaps.as<cf32>(); a.osc = h->wb.osc.as<cf32>(); a.om = h->wb.om.as<uint32_t>();
-    a.iq = h->s_iq_own.as<cf32>(); a.iq_stride = h->s_stride; a.ring = h->s_ring; a.w = written % h->s_ring;
-    a.P = 128 * h->wb.D; a.n_ens = h->cfg.n_ensembles; a.e_pad = h->wb.e_pad; a.abs_mod = (uint32_t)(h->wb.abs % a.P);
-    h->wb.abs += n; if (h->wb.n_taps > 1) h->wb.carry_sel ^= 1;
+    a.D = w.D; a.n_taps = w.n_taps; wideband_geometry(a); a.n_out = n / w.D;
+    a.ctaps = w.ctaps.as<cf32>(); a.osc = w.osc.as<cf32>(); a.om = w.om.as<uint32_t>();
+    a.P = 128 * w.D; a.n_ens = h->cfg.n_ensembles; a.e_pad = w.e_pad; a.abs_mod = (uint32_t)(h->wb.abs % a.P);
+    wideband_ends(h, raw, n, written, a.src, a.carry_out, a.dst);
     return a;
 }
 static int wideband_write_check(const dabphy_handle* h, const void* data, uint64_t n)
 {
     if (!h || !data) return DABPHY_ERR_INVALID;
-    if (!h->wb.on || !h->s_iq_own.p || h->s_iq != h->s_iq_own.as<cf32>()) return DABPHY_ERR_STATE;
-    if (h->wb.rational) return n == 0 || n >= h->wb.stage_samples || resample_outputs(h, n) > h->s_ring ? DABPHY_ERR_INVALID : DABPHY_OK;
-    if (n == 0 || n % h->wb.D || n / h->wb.D > h->s_ring) return DABPHY_ERR_INVALID;
-    return DABPHY_OK;
+    if (h->wb.kind == Wideband::OFF || !owns_ring(h)) return DABPHY_ERR_STATE;
+    if (h->wb.kind == Wideband::RATIONAL) return n == 0 || n >= h->wb.rational.stage_samples || resample_outputs(h, n) > h->s_ring ? DABPHY_ERR_INVALID : DABPHY_OK;
+    return n == 0 || n % h->wb.integer.D || n / h->wb.integer.D > h->s_ring ? DABPHY_ERR_INVALID : DABPHY_OK;
 }
 // queues one write's launches on `s` and says how many outputs they append; `keep`: dabphy_time_wideband runs these launches again
 static uint64_t wideband_launch(dabphy_handle* h, const void* raw, uint64_t n, uint64_t written, hipStream_t s, bool keep)
 {
-    if (h->wb.rational) {
+    if (keep) h->wb.last_valid = true;
+    if (h->wb.kind == Wideband::RATIONAL) {
         const ResampleArgs a = resample_args(h, raw, n, written);
-        if (keep) { h->wb.rs_last = a; h->wb.last_valid = true; }
+        if (keep) h->wb.rational.last = a;
         launch_resample(a, s);
         return a.n_out;
     }
     const WidebandArgs a = wideband_args(h, raw, n, written);
-    if (keep) { h->wb.last = a; h->wb.last_valid = true; }
+    if (keep) h->wb.integer.last = a;
     launch_wideband(a, s);
     return a.n_out;
 }
-static void wideband_launch_last(dabphy_handle* h) { if (h->wb.rational) launch_resample(h->wb.rs_last, h->stream); else launch_wideband(h->wb.last, h->stream); }
+static void wideband_launch_last(dabphy_handle* h) { if (h->wb.kind == Wideband::RATIONAL) launch_resample(h->wb.rational.last, h->stream); else launch_wideband(h->wb.integer.last, h->stream); }
 
 int dabphy_stream_write_wideband(dabphy_handle* h, const void* data, uint64_t n_capture_samples)
 {
@@ -423,9 +437,8 @@ int dabphy_stream_write_wideband(dabphy_handle* h, const void* data, uint64_t n_
     int r;
     if ((r = wideband_write_check(h, data, n_capture_samples))) return r;
     if (h->s_enqueued > h->s_valid) return DABPHY_ERR_STATE;     // asynchronous writes not committed: this one would not continue them
-    HIPCHK(h, hipStreamSynchronize(h->sync_stream));             // the chain that may be running ahead must not race with the write
-    HIPCHK(h, hipStreamSynchronize(h->copy_stream));             // ... and the carry of an asynchronous write in flight comes first
-    HIPCHK(h, hipMemcpyAsync(h->s_raw.p, data, (size_t)n_capture_samples * wideband_bps(h->wb.format), hipMemcpyHostToDevice, h->stream));
+    if ((r = writer_wait(h, true))) return r;
+    HIPCHK(h, hipMemcpyAsync(h->s_raw.p, data, (size_t)n_capture_samples * sample_bytes(h->wb.format), hipMemcpyHostToDevice, h->stream));
     h->s_valid += wideband_launch(h, h->s_raw.p, n_capture_samples, h->s_valid, h->stream, true);
     return sync(h);
 }
@@ -433,26 +446,17 @@ int dabphy_stream_write_wideband(dabphy_handle* h, const void* data, uint64_t n_
 int dabphy_stream_write_wideband_async(dabphy_handle* h, const void* data, uint64_t n_capture_samples)
 {
     DeviceBind dev_(h);
-    int r;
-    if ((r = wideband_write_check(h, data, n_capture_samples))) return r;
-    if (h->s_enqueued < h->s_valid) h->s_enqueued = h->s_valid;            // synchronous writes in between
-    const int slot = h->raw_sel; h->raw_sel ^= 1;
-    // the staging slot (and with it the host buffer of the call before last) is free once its previous conversion has run
-    HIPCHK(h, hipEventSynchronize(h->ev_ingest[slot]));
-    HIPCHK(h, hipMemcpyAsync(h->s_raw2[slot].p, data, (size_t)n_capture_samples * wideband_bps(h->wb.format), hipMemcpyHostToDevice, h->copy_stream));
-    const uint64_t n_out = wideband_launch(h, h->s_raw2[slot].p, n_capture_samples, h->s_enqueued, h->copy_stream, false);
-    HIPCHK(h, hipEventRecord(h->ev_ingest[slot], h->copy_stream));
-    h->s_enqueued += n_out;
-    return DABPHY_OK;
+    int r, slot;
+    if ((r = wideband_write_check(h, data, n_capture_samples)) || (r = stage_acquire(h, data, (size_t)n_capture_samples * sample_bytes(h->wb.format), &slot))) return r;
+    return stage_release(h, slot, wideband_launch(h, h->s_raw2[slot].p, n_capture_samples, h->s_enqueued, h->copy_stream, false));
 }
 
 int dabphy_time_wideband(dabphy_handle* h, uint32_t warmup, uint32_t iters, float* ms)
 {
     DeviceBind dev_(h);
     if (!h || !ms || iters == 0) return DABPHY_ERR_INVALID;
-    if (!h->wb.on || !h->wb.last_valid) return DABPHY_ERR_STATE;
-    HIPCHK(h, hipStreamSynchronize(h->sync_stream));
-    HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+    if (h->wb.kind == Wideband::OFF || !h->wb.last_valid) return DABPHY_ERR_STATE;
+    if (int r = writer_wait(h, true)) return r;
     ScopedEvent e0, e1;
     HIPCHK(h, e0.create()); HIPCHK(h, e1.create());
     for (uint32_t i = 0; i < warmup; i++) wideband_launch_last(h);

@@ -1,4 +1,4 @@
-// welle.io_amd/csrc/k_ingest.hip -- sample ingest: raw device-format IQ -> cf32 in the per-ensemble sample ring.
+// welle.io_amd/csrc/k_ingest.hip -- sample ingest: raw device-format IQ -> cf32 in the per-ensemble sample ring; the wideband front ends' carry.
 //
 // Replaces CRAWFile::convertSamples (input/raw_file.cpp:324-366), which every file/SDR front end of the reference
 // funnels through before OFDMProcessor sees a sample.  Converting on the GPU means 2 bytes per sample cross PCIe for
@@ -86,6 +86,18 @@ void launch_ingest(const IngestArgs& a, int n_ens, hipStream_t s)
 {
     const unsigned blocks = (unsigned)std::min<uint64_t>((a.n + 255) / 256, 4096);
     hipLaunchKernelGGL(k_ingest, dim3(blocks, n_ens), dim3(256), 0, s, a);
+}
+
+// The carry behind a write to a wideband stream, for either front end (CaptureSrc, dabphy_kernels.h): a call shorter than the carry keeps
+// part of the old one, which is why there are two buffers
+__global__ void __launch_bounds__(256) k_capture_carry(CaptureSrc c, cf32* carry_out)
+{
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < (int64_t)c.carry_len; q += (int64_t)gridDim.x * blockDim.x)
+        carry_out[q] = capture_sample(c, (int64_t)c.n - (int64_t)c.carry_len + q);
+}
+void launch_capture_carry(const CaptureSrc& c, cf32* carry_out, hipStream_t s)
+{
+    if (c.carry_len) hipLaunchKernelGGL(k_capture_carry, dim3((c.carry_len + 255) / 256), dim3(256), 0, s, c, carry_out);
 }
 
 } // namespace dabphy

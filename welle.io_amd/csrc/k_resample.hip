@@ -1,10 +1,11 @@
 // welle.io_amd/csrc/k_resample.hip -- wideband front end at a rational rate: one capture at 2.048 MS/s x M / L -> the sample ring rows of the
-// handle's ensembles.  ResampleArgs (dabphy_kernels.h) states the sum; k_wideband.hip is the integer case (L = 1) in another form.
+// handle's ensembles.  ResampleArgs (dabphy_kernels.h) states the sum; k_wideband.hip is the integer case (L = 1) in another form.  Both
+// read the capture through capture_sample (dabphy_kernels.h); the carry behind a call is k_capture_carry's (k_ingest.hip).
 //
 // Form: mix first, then filter with the real taps.  Consecutive outputs have different phases r_m, so a tap is a per-lane value and the
 // wave-uniform complex taps of k_wideband do not exist here; mixing first also halves the FMAs per tap (2 instead of 4 per ensemble).
 // A work-group owns a tile of T consecutive outputs, one per lane.  Per pass over G ensembles it converts the span of capture samples
-// the tile reaches (S = J + the samples T outputs advance over; carry in front of the call, zeros behind it) and writes it MIXED into
+// the tile reaches (S = J + the samples T outputs advance over; capture_sample: carry in front of the call, zeros behind it) and writes it MIXED into
 // LDS once per ensemble: G planes.  A thread walks its entries T apart and advances the capture index mod P by the constant T mod P
 // with add / compare / subtract; the oscillator is the product of two table entries (below).  Each lane then adds its taps
 // j = 0, 1, ... with one LDS read per ensemble and one tap load that serves all G (RS_TAP_STEP taps at a time, the next step's in
@@ -23,15 +24,6 @@
 
 namespace dabphy {
 
-__device__ __forceinline__ cf32 resample_sample(const ResampleArgs& A, int64_t gi)
-{
-    const int64_t C = (int64_t)A.J - 1;
-    cf32 v; v.re = 0.0f; v.im = 0.0f;
-    if (gi >= 0) { if ((uint64_t)gi < A.n) v = A.format == 0 ? reinterpret_cast<const cf32*>(A.raw)[gi] : ingest_sample(A.raw, (uint64_t)gi, A.format); }
-    else if (gi >= -C) v = A.carry_in[C + gi];
-    return v;
-}
-
 template <int G, int SMAX>
 __global__ void __launch_bounds__(256) k_resample(ResampleArgs A)
 {
@@ -47,7 +39,7 @@ __global__ void __launch_bounds__(256) k_resample(ResampleArgs A)
     const float* h_t = A.taps + r_t;                                              // taps[j][r]: the lanes of a wave read one row of L floats per tap
     const uint32_t row_top = s_top % Q, p_top = row_top * W + s_top / Q;
     const uint64_t m = t0 + t;
-    uint64_t ring_pos = A.w + m; if (ring_pos >= A.ring) ring_pos -= A.ring;
+    uint64_t ring_pos = A.dst.w + m; if (ring_pos >= A.dst.ring) ring_pos -= A.dst.ring;
 
     for (uint32_t e0 = 0; e0 < A.n_ens; e0 += G) {
         if (e0) __syncthreads();                                                  // the pass before has read its planes
@@ -74,7 +66,7 @@ __global__ void __launch_bounds__(256) k_resample(ResampleArgs A)
                 for (int u = 0; u < RS_MIX_STEP; u++) {
                     const uint32_t lu = l + u * T;
                     v[u].re = 0.0f; v[u].im = 0.0f;
-                    if (lu < A.S) v[u] = resample_sample(A, c0 + (int64_t)lu);
+                    if (lu < A.S) v[u] = capture_sample(A.src, c0 + (int64_t)lu);
                     p[u] = row * W + col; ix[u] = im;
                     im += im_step; if (im >= P) im -= P;
                     row += step_row; col += step_col;
@@ -119,18 +111,9 @@ __global__ void __launch_bounds__(256) k_resample(ResampleArgs A)
         if (m < A.n_out) {                                                        // (the last tile)
 #pragma unroll
             for (int g = 0; g < G; g++)
-                if (e0 + g < A.n_ens) { cf32 y; y.re = ar[g]; y.im = ai[g]; A.iq[(size_t)(e0 + g) * A.iq_stride + ring_pos] = y; }
+                if (e0 + g < A.n_ens) { cf32 y; y.re = ar[g]; y.im = ai[g]; A.dst.iq[(size_t)(e0 + g) * A.dst.iq_stride + ring_pos] = y; }
         }
     }
-}
-
-// The carry behind this call: the last J - 1 converted samples of (carry in front of it, the call's samples) -- a call shorter than the
-// filter keeps part of the old carry, which is why it is written to the OTHER buffer.
-__global__ void __launch_bounds__(256) k_resample_carry(ResampleArgs A)
-{
-    const int64_t C = (int64_t)A.J - 1;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < C; q += (int64_t)gridDim.x * blockDim.x)
-        A.carry_out[q] = resample_sample(A, (int64_t)A.n - C + q);
 }
 
 // The tile with the most outputs x ensembles whose planes fit RS_TILE_LARGE; of two such the one with more outputs (less of the span is
@@ -165,7 +148,7 @@ void launch_resample(const ResampleArgs& a, hipStream_t s)
         else if (a.G == 2) launch_resample_g<2>(a, tiles, s);
         else launch_resample_g<1>(a, tiles, s);
     }
-    hipLaunchKernelGGL(k_resample_carry, dim3((a.J - 1 + 255) / 256), dim3(256), 0, s, a);
+    launch_capture_carry(a.src, a.carry_out, s);
 }
 
 } // namespace dabphy

@@ -1,7 +1,8 @@
 // welle.io_amd/csrc/k_wideband.hip -- wideband front end: one capture at D x 2.048 MS/s -> the sample ring rows of the handle's ensembles.
 //
 // The reference has no channeliser (its one rate conversion is the Airspy's pair average, input/airspy_sdr.cpp:187-202); this is the
-// polyphase decimator a multi-block SDR capture needs in front of k_ingest's ring.  WidebandArgs (dabphy_kernels.h) states the sum.
+// polyphase decimator a multi-block SDR capture needs in front of k_ingest's ring.  WidebandArgs (dabphy_kernels.h) states the sum;
+// the capture is read through capture_sample (there too), the carry behind a call is k_capture_carry's (k_ingest.hip).
 //
 // Form: filter with per-ensemble complex taps, rotate each output once.  A work-group converts one tile of the capture into LDS once
 // (T D + halo samples, read from HBM once) and serves every ensemble from it: WB_ENS_STEP ensembles at a time, WB_OUT_STEP outputs
@@ -24,11 +25,6 @@
 
 namespace dabphy {
 
-__device__ __forceinline__ cf32 wideband_sample(const uint8_t* __restrict__ raw, uint64_t i, int format)
-{
-    return format == 0 ? reinterpret_cast<const cf32*>(raw)[i] : ingest_sample(raw, i, format);
-}
-
 template <int SMAX>
 __global__ void __launch_bounds__(256) k_wideband(WidebandArgs A)
 {
@@ -39,18 +35,13 @@ __global__ void __launch_bounds__(256) k_wideband(WidebandArgs A)
     const uint32_t grp = (uint32_t)uniform_i32((int)(threadIdx.x / lanes)), n_grp = 256 / lanes;
     const uint64_t m0 = (uint64_t)blockIdx.x * T;                       // the tile's first output
     const int64_t c0 = (int64_t)(m0 * D) - (int64_t)A.halo;             // capture index (in this call) of tile entry 0
-    const int64_t C = (int64_t)A.n_taps - 1;
 
-    // ---- the tile, converted once: the call's samples, the carry in front of them, zeros behind them (the last tile) and in front of the stream
+    // ---- the tile, converted once (capture_sample: the call's samples, the carry in front of them, zeros behind them in the last tile)
     {
         const uint32_t L = A.halo + T * D, step_row = 256 % D, step_col = 256 / D;
         uint32_t row = threadIdx.x % D, col = threadIdx.x / D;
         for (uint32_t l = threadIdx.x; l < L; l += 256) {
-            const int64_t gi = c0 + (int64_t)l;
-            cf32 v; v.re = 0.0f; v.im = 0.0f;
-            if (gi >= 0) { if ((uint64_t)gi < A.n) v = wideband_sample(A.raw, (uint64_t)gi, A.format); }
-            else if (gi >= -C) v = A.carry_in[C + gi];
-            tile[row * W + col] = v;
+            tile[row * W + col] = capture_sample(A.src, c0 + (int64_t)l);
             row += step_row; col += step_col;
             if (row >= D) { row -= D; col++; }
         }
@@ -113,7 +104,7 @@ __global__ void __launch_bounds__(256) k_wideband(WidebandArgs A)
         for (int o = 0; o < WB_OUT_STEP; o++) {
             const uint64_t m = m0 + t + o * lanes;
             if (m >= A.n_out) continue;                                 // (the last tile)
-            uint64_t p = A.w + m; if (p >= A.ring) p -= A.ring;
+            uint64_t p = A.dst.w + m; if (p >= A.dst.ring) p -= A.dst.ring;
             // the oscillator's phase at the output's newest sample a = m D + D - 1: table index (om_e * (a mod P)) mod P, both factors below 4096
             const uint32_t a_mod = (uint32_t)(((uint64_t)A.abs_mod + (m * D + D - 1) % A.P) % A.P);
 #pragma unroll
@@ -121,21 +112,10 @@ __global__ void __launch_bounds__(256) k_wideband(WidebandArgs A)
                 const uint32_t e = e0 + q;
                 if (e < A.n_ens) {
                     cf32 acc; acc.re = ar[o][q]; acc.im = ai[o][q];
-                    A.iq[(size_t)e * A.iq_stride + p] = cmul(acc, A.osc[(A.om[e] * a_mod) % A.P]);
+                    A.dst.iq[(size_t)e * A.dst.iq_stride + p] = cmul(acc, A.osc[(A.om[e] * a_mod) % A.P]);
                 }
             }
         }
-    }
-}
-
-// The carry behind this call: the last n_taps - 1 converted samples of (carry in front of it, the call's samples) -- a call shorter than
-// the filter keeps part of the old carry, which is why it is written to the OTHER buffer.
-__global__ void __launch_bounds__(256) k_wideband_carry(WidebandArgs A)
-{
-    const int64_t C = (int64_t)A.n_taps - 1;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < C; q += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t gi = (int64_t)A.n - C + q;
-        A.carry_out[q] = gi >= 0 ? wideband_sample(A.raw, (uint64_t)gi, A.format) : A.carry_in[C + gi];
     }
 }
 
@@ -155,7 +135,7 @@ void launch_wideband(const WidebandArgs& a, hipStream_t s)
     if ((size_t)a.D * a.W <= (size_t)WB_TILE_SMALL) hipLaunchKernelGGL(k_wideband<WB_TILE_SMALL>, dim3(tiles), dim3(256), 0, s, a);
     else if ((size_t)a.D * a.W <= (size_t)WB_TILE_MID) hipLaunchKernelGGL(k_wideband<WB_TILE_MID>, dim3(tiles), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_wideband<WB_TILE_LARGE>, dim3(tiles), dim3(256), 0, s, a);
-    if (a.n_taps > 1) hipLaunchKernelGGL(k_wideband_carry, dim3((a.n_taps - 1 + 255) / 256), dim3(256), 0, s, a);
+    launch_capture_carry(a.src, a.carry_out, s);
 }
 
 } // namespace dabphy

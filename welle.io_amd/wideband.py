@@ -9,6 +9,13 @@ RATE = 2048000
 OFFSET_UNIT_HZ = RATE // 128            # 16 kHz: every DAB block centre is a multiple of it
 
 
+def _kaiser_lowpass(n, rate_multiple, beta):
+    """n float64 taps of a windowed-sinc Kaiser low-pass with its cutoff at 1.024 MHz, at rate_multiple x 2.048 MS/s; not normalised"""
+    fc = 1024000.0 / (rate_multiple * float(RATE))           # cycles per sample
+    k = np.arange(n, dtype=np.float64) - (n - 1) / 2.0
+    return 2.0 * fc * np.sinc(2.0 * fc * k) * np.kaiser(n, float(beta))
+
+
 def design_taps(decimation, taps_per_branch=16, beta=8.0):
     """Windowed-sinc Kaiser low-pass for a capture at decimation x 2.048 MS/s: taps_per_branch * decimation real taps (float32), unit DC
     gain, computed in float64.  Cutoff 1.024 MHz: the transition may run from 768 kHz, the edge of the DAB signal, to 1 280 kHz, the
@@ -17,51 +24,17 @@ def design_taps(decimation, taps_per_branch=16, beta=8.0):
     decimation = int(decimation); n = int(taps_per_branch) * decimation
     if decimation < 1 or n < 1:
         raise ValueError("design_taps: decimation and taps_per_branch must be positive")
-    fc = 1024000.0 / (decimation * float(RATE))              # cycles per capture sample
-    k = np.arange(n, dtype=np.float64) - (n - 1) / 2.0
-    h = 2.0 * fc * np.sinc(2.0 * fc * k) * np.kaiser(n, float(beta))
+    h = _kaiser_lowpass(n, decimation, beta)
     return (h / h.sum()).astype(np.float32)
-
-
-def upsample(x, decimation, pad_to=4096):
-    """x at 2.048 MS/s -> decimation x that rate by zero-padding its spectrum (exact for the band-limited streams of synth.make_stream);
-    the stream is first padded with zeros to a multiple of pad_to samples"""
-    x = np.asarray(x, np.complex128)
-    n = -(-len(x) // pad_to) * pad_to
-    X = np.fft.fft(np.concatenate([x, np.zeros(n - len(x), np.complex128)]))
-    if decimation == 1:
-        return np.fft.ifft(X)
-    Y = np.zeros(n * decimation, np.complex128)
-    Y[:n // 2] = X[:n // 2]; Y[-(n // 2):] = X[n // 2:]
-    return np.fft.ifft(Y) * decimation
-
-
-def oscillator(offset, n, decimation, sign=+1):
-    """exp(sign * 2 pi j * offset * 16 kHz * i / (decimation * 2.048 MHz)) for i < n, from the exact phase (offset * i) mod (128 * decimation)"""
-    P = 128 * int(decimation)
-    ph = (np.arange(n, dtype=np.int64) * int(offset)) % P
-    return np.exp(sign * 2j * np.pi * ph / P)
 
 
 def synth_capture(streams, offsets, decimation, snr_db=None, seed=0, amplitude=0.25):
     """One capture (complex128, at decimation x 2.048 MS/s) out of noise-free 2.048 MS/s streams (synth.make_stream without snr_db): each
-    is upsampled, shifted up by its offset x 16 kHz, and all are summed; white noise is added so that every channel sees snr_db in ITS
-    2.048 MHz (a signal of power amplitude ** 2: the noise power of the capture is decimation times the channel's).  The length is that
-    of the longest stream, rounded up to a multiple of 4 096, times the decimation."""
-    if len(streams) != len(offsets):
-        raise ValueError("synth_capture: %d streams, %d offsets" % (len(streams), len(offsets)))
-    n = max(len(s) for s in streams)
-    cap = None
-    for s, off in zip(streams, offsets):
-        s = np.concatenate([np.asarray(s, np.complex128), np.zeros(n - len(s), np.complex128)])
-        u = upsample(s, decimation)
-        u *= oscillator(off, len(u), decimation)
-        cap = u if cap is None else cap + u
-    if snr_db is not None:
-        rng = np.random.RandomState(seed)
-        sigma = np.sqrt(decimation * amplitude ** 2 / (10 ** (snr_db / 10.0)) / 2)
-        cap = cap + sigma * (rng.randn(len(cap)) + 1j * rng.randn(len(cap)))
-    return cap
+    is upsampled by zero-padding its spectrum (exact for these band-limited streams), shifted up by its offset x 16 kHz, and all are
+    summed; white noise is added so that every channel sees snr_db in ITS 2.048 MHz (a signal of power amplitude ** 2: the noise power
+    of the capture is decimation times the channel's).  The length is that of the longest stream, rounded up to a multiple of 4 096,
+    times the decimation.  (synth_capture_rational with interpolation 1: the same samples, bit for bit.)"""
+    return synth_capture_rational(streams, offsets, 1, decimation, snr_db=snr_db, seed=seed, amplitude=amplitude)
 
 
 def design_taps_rational(interpolation, decimation, periods=16, beta=8.0):
@@ -72,14 +45,12 @@ def design_taps_rational(interpolation, decimation, periods=16, beta=8.0):
     L, M = int(interpolation), int(decimation); n = int(round(periods * M))
     if L < 1 or M < L or n < 1:
         raise ValueError("design_taps_rational: needs 1 <= interpolation <= decimation and a positive length")
-    fc = 1024000.0 / (M * float(RATE))                        # cycles per sample of the prototype's rate
-    k = np.arange(n, dtype=np.float64) - (n - 1) / 2.0
-    h = 2.0 * fc * np.sinc(2.0 * fc * k) * np.kaiser(n, float(beta))
+    h = _kaiser_lowpass(n, M, beta)                           # (at the prototype's rate)
     return (h * (L / h.sum())).astype(np.float32)
 
 
 def synth_capture_rational(streams, offsets, interpolation, decimation, snr_db=None, seed=0, amplitude=0.25):
-    """synth_capture at 2.048 MS/s x decimation / interpolation: every stream's spectrum (padded to n points, a multiple of 4 096 and
+    """The same at 2.048 MS/s x decimation / interpolation: every stream's spectrum (padded to n points, a multiple of 4 096 and
     of the interpolation) is zero-padded to n * decimation / interpolation points, the stream shifted up by its offset x 16 kHz --
     (offset * interpolation * i) mod P of P = 128 * decimation cycles at capture sample i -- and white noise of decimation /
     interpolation times the channel's power added, so that every channel sees snr_db in ITS 2.048 MHz."""
