@@ -60,7 +60,7 @@ uint32_t dabphy_abi_version(void);
 typedef enum { DABPHY_STRUCT_CONFIG = 0, DABPHY_STRUCT_FRAME_INFO = 1, DABPHY_STRUCT_SF_EVENT = 2, DABPHY_STRUCT_SUBCHANNEL = 3,
                DABPHY_STRUCT_PROTECTION = 4, DABPHY_STRUCT_TII_MEASUREMENT = 5, DABPHY_STRUCT_MSC_DESC = 6,
                DABPHY_STRUCT_MP2_EVENT = 7, DABPHY_STRUCT_AU_SERVICE = 8, DABPHY_STRUCT_AU_DESC = 9,
-               DABPHY_STRUCT_WIDEBAND_CONFIG = 10, DABPHY_STRUCT_RESAMPLER_CONFIG = 11 } dabphy_struct_id;
+               DABPHY_STRUCT_WIDEBAND_CONFIG = 10, DABPHY_STRUCT_RESAMPLER_CONFIG = 11, DABPHY_STRUCT_BER_COUNT = 12 } dabphy_struct_id;
 size_t dabphy_struct_size(int32_t which);      /* 0 for an unknown id */
 
 /* RadioReceiverOptions (src/backend/radio-receiver-options.h:66-84) + batch geometry */
@@ -623,6 +623,47 @@ int dabphy_au_drain_begin(dabphy_handle* h, dabphy_au_service* services, uint32_
 int dabphy_au_drain_wait(dabphy_handle* h, uint32_t* n_services, uint32_t* n_aus);
 int dabphy_get_au_batch(dabphy_handle* h, dabphy_au_service* services, uint32_t services_capacity, dabphy_au_desc* aus, uint32_t aus_capacity,
                         uint8_t* buf, size_t buf_capacity, uint32_t* n_services, uint32_t* n_aus);
+
+/* ---- Channel BER (pseudo-BER): the bit error ratio in front of the Viterbi decoder, per code word -------------------------------------
+ * The decoded bits of a code word are encoded again with the mother code and compared with the SIGNS of the received soft bits at the
+ * positions that were transmitted.  No known payload is needed; the figure grades a channel from 1e-1 down to 0, per sub-channel and
+ * for the FIC, where the FIC ratio, the RS totals and the CRCs all read "perfect".  Definition, for a code word of nbits decoded bits
+ * (nbits + 6 trellis steps):
+ *   1. the decoded bits as the getters return them (packed MSB first), energy dispersal put back (XOR with the PRBS the decoder removed);
+ *   2. step s has the register d[s], d[s-1], ..., d[s-6] (bits in front of the code word and the six tail inputs are 0, the newest bit
+ *      is the LSB); coded bit j = parity(register & {0155, 0117, 0123, 0155}[j]);
+ *   3. mother-code bit m = 4 s + j is compared where the puncturing transmitted it (the 24 tail bits included: PI_X keeps 12) and its
+ *      soft bit exists -- the byte the decoder read for it: through the time de-interleaver for the MSC, the quarter of symbols 1..3
+ *      for the FIC.  A CIF from before the stream or a frame that is not valid == 1 has no soft bits;
+ *   4. a soft bit of 0 is not counted; otherwise compared += 1, the hard decision is 1 iff the soft bit is > 0 (+127 = coded bit 1;
+ *      -128 counts as negative like -127), errors += 1 where it differs from the encoded bit.
+ * With no zero soft bit and every row present, compared == dabphy_protection_input_bits(prot) (2304 for a FIC code word).
+ * The counts describe the decoder's OUTPUT: where the decoder fails they are the distance to the code word it chose, a LOWER bound
+ * of the channel's bit error ratio (the known property of the method).
+ *
+ * dabphy_set_channel_ber(h, 1) makes every following dabphy_process count the batch behind its final decode (in exact batch mode:
+ * behind the replay, so the counts always belong to the bytes the getters return); off (the default) nothing is launched, allocated
+ * or changed.  The getters then describe the LAST batch; with the feature off, or before a batch has been counted (after
+ * dabphy_reset, a new sub-channel list, switching on), they return DABPHY_ERR_STATE.
+ *   dabphy_get_channel_ber_fic        out [n_ensembles][n_frames][4]: the four code words of every frame's FIC
+ *   dabphy_get_channel_ber_ensemble   out [4 * n_frames] rows of one ensemble's sub-channel; first_valid / n_rows exactly as
+ *                                     dabphy_get_msc_ensemble reports them; rows outside [first_valid, n_rows) are {0, 0}
+ *   dabphy_get_channel_ber_totals     errors, compared [n_ensembles][*row_len], row_len = 1 + the longest sub-channel list: slot 0 =
+ *                                     the FIC, slot 1 + i = list position i of that ensemble (0 where the list is shorter): the sums
+ *                                     over the batch, reduced on the device -- one small array per step for a monitor
+ *                                     (errors == compared == NULL: only *row_len, what the arrays must hold, is returned)
+ * dabphy_channel_ber is the stateless entry (it works with the feature on or off): n_codewords code words of one profile,
+ *   in      [n_codewords][dabphy_protection_input_bits(prot)] punctured soft bits as dabphy_msc_deconvolve takes them (prot from
+ *           dabphy_protection_fic for a FIC quarter),
+ *   decoded [n_codewords][nbits / 8] bytes as dabphy_msc_deconvolve / dabphy_fic_decode return them. */
+typedef struct { uint32_t errors, compared; } dabphy_ber_count;
+int dabphy_set_channel_ber(dabphy_handle* h, int32_t on);
+int dabphy_channel_ber(dabphy_handle* h, const dabphy_protection* prot, const int8_t* in, const uint8_t* decoded,
+                       uint32_t n_codewords, dabphy_ber_count* out);
+int dabphy_get_channel_ber_fic(dabphy_handle* h, dabphy_ber_count* out);
+int dabphy_get_channel_ber_ensemble(dabphy_handle* h, uint32_t ensemble, uint32_t subch_index, dabphy_ber_count* out,
+                                    size_t out_capacity /* records */, int32_t* first_valid, int32_t* n_rows);
+int dabphy_get_channel_ber_totals(dabphy_handle* h, uint64_t* errors, uint64_t* compared, uint32_t* row_len);
 
 /* ---- TIIDecoder (tii-decoder.cpp:189-383), fed by OFDMProcessor::run with the PRS and the trailing NULL symbol of every
  * frame (ofdm-processor.cpp:381-386,462-466) when RadioReceiverOptions::decodeTII is set (radio-receiver-options.h:75; welle-cli

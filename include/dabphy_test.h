@@ -24,6 +24,8 @@ int dabphy_time_viterbi(dabphy_handle* h, uint32_t nbits, uint32_t n_codewords, 
 int dabphy_time_fused_msc(dabphy_handle* h, uint32_t iters, float* ms);
 /* dabphy_get_mp2_ms: device time of the last MP2 pass (dabphy_mp2_stats / dabphy_set_auto_mp2) run with dabphy_set_profiling on; 0 if none */
 int dabphy_get_mp2_ms(dabphy_handle* h, float* ms);
+/* dabphy_get_chanber_ms: device time of the last channel BER pass (dabphy_set_channel_ber; both kernels) queued with dabphy_set_profiling on; 0 if none */
+int dabphy_get_chanber_ms(dabphy_handle* h, float* ms);
 /* EXPERIMENT of round 6, off by default (profiles/r06_viterbi_split.txt: a measured loss).  on = 1: the forward waves of the lane-per-code-word
  * Viterbi kernel publish every group's decisions (per-group scratch, agent-scope release, a flag) and walk back only when no trellis is left
  * to run -- the walks of the whole launch then overlap the forward passes of other waves instead of following each group's own.  Same bytes,

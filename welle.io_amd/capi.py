@@ -60,6 +60,7 @@ SYNC_SERIAL, SYNC_WIDE, SYNC_CHAIN = 0, 1, 2                                # da
 SYNC_CASE = 4096                                                            # DABPHY_TEST_SYNC_CASE
 SYNC_DESC_DTYPE = np.dtype([("pos", "<i8"), ("start_index", "<i4"), ("valid", "<i4"), ("coarse_ran", "<i4"), ("coarse_after", "<i4"), ("coarse_step", "<i4"), ("L1", "<i4")])   # dabphy_test_sync_desc
 SYNC_STATE_DTYPE = np.dtype([("pos", "<i8"), ("synced", "<i4"), ("lost", "<i4")])                                                  # dabphy_test_sync_state
+BER_COUNT_DTYPE = np.dtype([("errors", "<u4"), ("compared", "<u4")])                # dabphy_ber_count
 AU_OFF, AU_RAW, AU_LOAS = 0, 1, 2                                           # dabphy_set_au_drain
 AU_SERVICE_DTYPE = np.dtype([("ensemble", "<u4"), ("subch_index", "<u4"), ("subch_id", "<u4"), ("n_superframes", "<i4"), ("n_aus", "<i4"), ("n_failed", "<i4"),
                              ("first_au", "<u4"), ("pad_", "<u4"), ("offset", "<u8"), ("bytes", "<u8")])      # dabphy_au_service
@@ -497,6 +498,48 @@ class DabPhy:
         ev = np.zeros((S, max(cap, 1)), MP2_EVENT_DTYPE); ne = np.zeros(S, np.int32); fe = np.zeros((S, nf), np.int32); fu = np.zeros(S, np.int32)
         self._chk(self.lib.dabphy_mp2_check(self.h, _p(frames), C.c_uint32(S), C.c_uint32(nf), C.c_uint32(frame_len), _p(ev), C.c_int32(cap), _p(ne), _p(fe), _p(fu)))
         return [ev[s, :min(ne[s], cap)] for s in range(S)], ne, fe, fu
+
+    # ---- channel BER (pseudo-BER) in front of the Viterbi decoder
+    def set_channel_ber(self, on=True):
+        self._chk(self.lib.dabphy_set_channel_ber(self.h, int(on)))
+
+    def channel_ber(self, prot, soft, decoded):
+        """stateless entry (dabphy_channel_ber): punctured soft bits [n][input bits] and the decoded bytes [n][nbits / 8] -> BER_COUNT_DTYPE [n]"""
+        nin = self.protection_input_bits(prot)
+        soft = np.ascontiguousarray(soft, np.int8).reshape(-1, nin)
+        decoded = np.ascontiguousarray(decoded, np.uint8).reshape(-1, prot.nbits // 8)
+        n = soft.shape[0]
+        if decoded.shape[0] != n:
+            raise DabPhyError("channel_ber: %d code words of soft bits, %d of decoded bytes" % (n, decoded.shape[0]))
+        out = np.zeros(n, BER_COUNT_DTYPE)
+        self._chk(self.lib.dabphy_channel_ber(self.h, C.byref(prot), _p(soft), _p(decoded), C.c_uint32(n), _p(out)))
+        return out
+
+    def channel_ber_fic(self):
+        """-> BER_COUNT_DTYPE [B][F][4] of the last batch"""
+        out = np.zeros((self.cfg.n_ensembles, getattr(self, "_last", 0) or 1, 4), BER_COUNT_DTYPE)      # (before the first process(): the library refuses)
+        self._chk(self.lib.dabphy_get_channel_ber_fic(self.h, _p(out)))
+        return out
+
+    def channel_ber_ensemble(self, ensemble, idx):
+        """-> (BER_COUNT_DTYPE [4F], first_valid, n_rows) of sub-channel idx of one ensemble"""
+        out = np.zeros(4 * (getattr(self, "_last", 0) or 1), BER_COUNT_DTYPE); fv = C.c_int32(0); nr = C.c_int32(0)
+        self._chk(self.lib.dabphy_get_channel_ber_ensemble(self.h, ensemble, idx, _p(out), C.c_size_t(len(out)), C.byref(fv), C.byref(nr)))
+        return out, fv.value, nr.value
+
+    def channel_ber_totals(self):
+        """-> (errors, compared) uint64 [B][1 + longest list]: slot 0 the FIC, slot 1 + i list position i"""
+        n = C.c_uint32(0)
+        self._chk(self.lib.dabphy_get_channel_ber_totals(self.h, None, None, C.byref(n)))
+        e = np.zeros((self.cfg.n_ensembles, n.value), np.uint64); c = np.zeros_like(e)
+        self._chk(self.lib.dabphy_get_channel_ber_totals(self.h, _p(e), _p(c), C.byref(n)))
+        return e, c
+
+    def chanber_ms(self):
+        """device time of the last channel BER pass queued with profiling on"""
+        ms = C.c_float(0)
+        self._chk(self.lib.dabphy_get_chanber_ms(self.h, C.byref(ms)))
+        return ms.value
 
     def host_alloc(self, shape, dtype):
         """page-locked numpy array (dabphy_host_alloc); release with host_free(arr)"""

@@ -21,6 +21,7 @@ size_t dabphy_struct_size(int32_t which)
         case DABPHY_STRUCT_AU_DESC: return sizeof(dabphy_au_desc);
         case DABPHY_STRUCT_WIDEBAND_CONFIG: return sizeof(dabphy_wideband_config);
         case DABPHY_STRUCT_RESAMPLER_CONFIG: return sizeof(dabphy_resampler_config);
+        case DABPHY_STRUCT_BER_COUNT: return sizeof(dabphy_ber_count);
     }
     return 0;
 }
@@ -359,7 +360,7 @@ int dabphy_set_subchannels(dabphy_handle* h, const dabphy_subchannel* list, uint
     for (auto& l : h->subch_next) l.assign(list, list + n);
     for (auto& k : h->kind_next) k.assign(n, DABPHY_AUDIO_DABPLUS);     // (a new list: every position DAB+ until kinds are set again)
     h->kinds_dirty = true;
-    h->subch_dirty = true;
+    h->subch_dirty = true; chanber_clear(h);
     return apply_subchannels(h);
 }
 
@@ -375,7 +376,7 @@ int dabphy_set_subchannels_ensemble(dabphy_handle* h, uint32_t ensemble, const d
     h->subch_next[ensemble].assign(list, list + n);
     h->kind_next[ensemble].assign(n, DABPHY_AUDIO_DABPLUS);
     h->kinds_dirty = true;
-    h->subch_dirty = true;
+    h->subch_dirty = true; chanber_clear(h);
     return DABPHY_OK;
 }
 

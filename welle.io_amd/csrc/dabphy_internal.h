@@ -8,6 +8,7 @@
 //   dabphy_mp2.hip          classic DAB (MP2) services: audio kinds, the MP2 frame check and its unit entry
 //   dabphy_getters.hip      everything a caller reads back after a batch, profiling, TII
 //   dabphy_au.hip           the bulk access-unit drain: the pack pass behind the filter (k_au.hip), its tables and its copy to the host
+//   dabphy_chanber.hip      the channel BER pass (k_chanber.hip): tables, the launch behind a batch's final decode, getters, the stateless entry
 //   k_sync.hip              the synchroniser's kernels, with one header per reference function: sync_window.h (PhaseReference::findIndex:
 //                           impulse response, the three window-index methods), sync_fine.h (the fine corrector's step and its interval test; host-compilable); block_reduce.h (their work-group reduction)
 //   k_wideband.hip, k_resample.hip   the wideband front end's main kernels (integer, rational rate); capture_sample (dabphy_kernels.h) and k_capture_carry (k_ingest.hip) serve both
@@ -254,6 +255,17 @@ struct dabphy_handle {
         AuSvc* h_svc = nullptr; size_t h_svc_cap = 0;                // page-locked landing area of the service records
         dabphy_au_service* out_services = nullptr; bool out_aus = false;
     } au;
+    // Channel BER pass (dabphy_chanber.hip, k_chanber.hip; dabphy_set_channel_ber): the decoded bits encoded again and compared with the
+    // signs of the soft bits, behind the batch's final decode.  Nothing here is allocated or launched while it is off.  The counts
+    // are per batch: nothing is carried, exact batch mode has nothing to put back.
+    struct ChanBer {
+        bool on = false, counted = false;                            // counted: counts / totals are the last batch's (dabphy_reset, a new list and switching on clear it)
+        uint32_t F = 0, row_len = 0;                                 // geometry of the tables below: batch depth, 1 + the longest list
+        DevBuf cls, work, first, slots, counts, totals;              // classes (the FIC last), groups of 64 code words, first record per class, first record per totals slot
+        std::vector<FusedClass> host_cls; std::vector<uint32_t> host_work, host_first, host_slots;   // what the device tables hold
+        hipEvent_t ev[2] = {nullptr, nullptr}; bool timed = false;   // the last pass, with profiling on (dabphy_get_chanber_ms)
+    } ber;
+    DevBuf ber_lin_tab, ber_lin_out;                                 // dabphy_channel_ber (the stateless entry): its class, work list and counts
     DevBuf tii_rot, tii_rank, tii_pat, tii_err, tii_likely, tii_state, tii_events, tii_nev;     // (tii_state: [B][TII_SLOTS] sums, then [B] dropped-measurement counters -- one carried block)
     uint32_t tii_max_events = 0;
 };
@@ -493,5 +505,8 @@ DABPHY_INTERNAL int drain_stream_ready(dabphy_handle* h);                       
 DABPHY_INTERNAL int au_pack_pass(dabphy_handle* h, const std::vector<SfSel>& sel, hipStream_t st, uint32_t F);   // dabphy_au.hip: the pack pass behind a filter pass over `sel` (nothing when the drain is off)
 DABPHY_INTERNAL int au_drain_wait(dabphy_handle* h);                                             // ... host waits for an access-unit drain in flight
 DABPHY_INTERNAL int drain_wait(dabphy_handle* h);                                                // dabphy_getters.hip: host waits for a bulk MSC drain in flight
-DABPHY_INTERNAL size_t soft_ens_stride(const dabphy_handle* h);                                   // bytes between the soft-bit ring slices of two ensembles
+DABPHY_INTERNAL int chanber_reserve(dabphy_handle* h, uint32_t F);                               // dabphy_chanber.hip: the pass's buffers and tables for this batch depth (nothing while it is off)
+DABPHY_INTERNAL int chanber_pass(dabphy_handle* h, const FrameDesc* desc, uint32_t F);           // ... the pass over the batch just decoded, on the main stream
+DABPHY_INTERNAL void chanber_clear(dabphy_handle* h);                                            // ... its results are no longer the last batch's
+DABPHY_INTERNAL size_t soft_ens_stride(const dabphy_handle* h);                                  // bytes between the soft-bit ring slices of two ensembles
 }

@@ -231,6 +231,15 @@ constexpr int SP2_VARIANTS = 2;
 void launch_viterbi_sp2(const FusedArgs& a, int lds_variant, hipStream_t s);
 void launch_selftest_half_exchange(unsigned* out, hipStream_t s);
 
+// Channel BER pass (k_chanber.hip): one wavefront per code word of f.work's groups (class << 24 | group of 64, as the decoders list
+// them); f names what locate() reads -- the soft-bit ring and the descriptors, or a seam's plain array --, the classes (map, pairs, out,
+// nbits, dedisperse) and the PRBS words.  Code word cw of class c -> out[first[c] + cw] = (errors, compared)
+struct BerArgs { FusedArgs f; const uint32_t* first; uint2* out; };
+// ... and its totals: slot i sums the n records from counts[slots[i]] on (0xffffffff: none) into totals[2 i], totals[2 i + 1]
+struct BerTotalsArgs { const uint2* counts; const uint32_t* slots; uint32_t n; uint64_t* totals; };
+void launch_chanber(const BerArgs& a, hipStream_t s);
+void launch_chanber_totals(const BerTotalsArgs& a, int n_slots, hipStream_t s);
+
 struct CrcArgs {
     const uint8_t* fib;     // [B][F][12][32]
     uint8_t* ok;            // [B][F][12]

@@ -114,6 +114,7 @@ static int reserve_batch(dabphy_handle* h, const Batch& b)
         for (int k = 0; k < dabphy_handle::N_DESC; k++) if ((r = for_each_carried_sync(h, k, reserve))) return r;
         if ((r = for_each_carried(h, false, reserve))) return r;
     }
+    if ((r = chanber_reserve(h, F))) return r;                // (dabphy_set_channel_ber: tables over the class outputs as they now lie)
     // (an ensure() above may have moved a buffer the plan names: then it is stale -- plan again, nothing moves the second time)
     if (h->fplan.buf_gen != h->buf_gen && (r = fused_plan(h, F, true))) return r;
     // split traceback: the page-locked word the walkers' give-up count comes back in
@@ -357,6 +358,7 @@ static int replay_batch(dabphy_handle* h, Batch& b)
     if ((r = restore_carried(h, b.cur))) return r;
     if ((r = decode_batch(h, b, true))) return r;
     if ((r = finish_pass(h))) return r;
+    if ((r = chanber_pass(h, b.d_desc, b.F))) return r;       // (the counts of the first pass are replaced: they belong to the bytes the getters return)
     if ((r = sync(h))) return r;
     // the batches synchronised ahead started from the state the first pass left: again, from the right one.  (The chain reads the
     // FIC ratio: the main stream has just been drained.)
@@ -429,6 +431,7 @@ int dabphy_process(dabphy_handle* h, uint32_t n_frames)
     if (b.depth && (r = queue_next_chains(h, b))) return r;  // (behind the decoder, unless decode_batch queued them in front of it)
     h->desc_sel = (cur + 1) % dabphy_handle::N_DESC; h->ahead--;
     if ((r = finish_pass(h))) return r;
+    if ((r = chanber_pass(h, b.d_desc, F))) return r;         // dabphy_set_channel_ber: behind every decoder of the batch, in front of the wait below (dabphy_chanber.hip: "Order")
     tick(h, b, 3);
     if ((r = sync(h))) return r;
     tick(h, b, 4);

@@ -152,7 +152,7 @@ int dabphy_reset(dabphy_handle* h)
     // TIIDecoder); the pair tables and their cif0 below are reset too but are no snapshot of exact batch mode, so they stand apart
     r = for_each_carried(h, true, [&](void* live, DevBuf&, size_t bytes) -> int { if (live) HIPCHK(h, hipMemsetAsync(live, 0, bytes, h->stream)); return 0; });
     if (r) return r;
-    h->mp2_done = false;
+    h->mp2_done = false; chanber_clear(h);
     // ... and the frame count starts over: every selected sub-channel's time de-interleaver fills again from the first CIF decoded
     for (auto& c : h->classes) { for (MscPair& p : c.pairs) p.cif0 = -1; int r2 = upload_pairs(h, c); if (r2) return r2; }
     h->tii_ran = false;
