@@ -22,6 +22,14 @@ int dabphy_time_demod(dabphy_handle* h, const float* frames, uint32_t n_src, uin
 int dabphy_time_viterbi(dabphy_handle* h, uint32_t nbits, uint32_t n_codewords, uint32_t iters, float* ms_gather,
                         float* ms_decode);
 int dabphy_time_fused_msc(dabphy_handle* h, uint32_t iters, float* ms);
+/* dabphy_time_superframe_wide: re-runs the wide launches (k_superframe_wide, one per LDS bucket) of the last DAB+ superframe filter pass -- of
+ *   dabphy_process with dabphy_set_auto_superframes, dabphy_superframes_stats or dabphy_superframes; a deferred pass that still waits runs
+ *   first -- `iters` times with nothing else on the device; *ms = mean time of one repetition.  The kernel only reads the windows and the class
+ *   outputs, but the pass' settle kernel has moved the windows on since: a repetition therefore leaves out, per sub-channel, the one attempt
+ *   that began in frames carried into the batch (at 32 frames per batch 25 of 26 attempts, or all 25, are made again) and every sub-channel the
+ *   serial walk took; each other attempt rewrites its event and superframe with the values they hold.  DABPHY_ERR_STATE before the first
+ *   pass and after anything that replaced a buffer the launches name (dabphy_set_subchannels, a larger batch). */
+int dabphy_time_superframe_wide(dabphy_handle* h, uint32_t iters, float* ms);
 /* dabphy_get_mp2_ms: device time of the last MP2 pass (dabphy_mp2_stats / dabphy_set_auto_mp2) run with dabphy_set_profiling on; 0 if none */
 int dabphy_get_mp2_ms(dabphy_handle* h, float* ms);
 /* dabphy_get_chanber_ms: device time of the last channel BER pass (dabphy_set_channel_ber; both kernels) queued with dabphy_set_profiling on; 0 if none */

@@ -324,6 +324,12 @@ class DabPhy:
         self._chk(self.lib.dabphy_time_fused_msc(self.h, iters, C.byref(a)))
         return a.value
 
+    def time_superframe_wide(self, iters=3):
+        """mean device time [ms] of the last filter pass' wide launches run again alone (dabphy_time_superframe_wide)"""
+        a = C.c_float(0)
+        self._chk(self.lib.dabphy_time_superframe_wide(self.h, iters, C.byref(a)))
+        return a.value
+
     # ---- streaming receiver
     def reset(self):
         self._chk(self.lib.dabphy_reset(self.h))

@@ -108,7 +108,7 @@ int dabphy_get_wide_superframe_stats(dabphy_handle* h, uint64_t* settled, uint64
     if (!h) return DABPHY_ERR_INVALID;
     unsigned long long v[2] = {0, 0};
     if (h->sf_gf.p) {
-        HIPCHK(h, hipMemcpyAsync(v, h->sf_gf.as<uint8_t>() + 512, sizeof v, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(v, h->sf_gf.as<uint8_t>() + RS_WIDE_STATS_OFF, sizeof v, hipMemcpyDeviceToHost, h->stream));
         int r = sync(h); if (r) return r;
     }
     if (settled) *settled = v[0];

@@ -152,6 +152,8 @@ struct dabphy_handle {
     // bulk MSC drain (dabphy_msc_drain_begin / _wait): the class outputs leave on a stream of their own while the next batch starts
     hipStream_t drain_stream = nullptr; hipEvent_t ev_drain_done = nullptr, ev_drain_staged = nullptr; bool drain_pending = false; DevBuf drain_stage;
     DevBuf sf_events, sf_count, sf_bytes, sf_stats, sf_gf, sf_accept; const FrameDesc* last_desc = nullptr;
+    // the wide launches of the last filter pass, per bucket, as they were queued (dabphy_time_superframe_wide re-runs them alone while buf_gen is current)
+    struct SfWideLaunch { SfBatch bt{}; int blocks = 0, n_cif = 0, max_s = 0; } sf_wide_last[3]; uint64_t sf_wide_gen = 0;
     static constexpr int N_DESC = 3;    // descriptor buffers: the batch being decoded + up to two synchronised ahead
     DevBuf s_desc2[N_DESC], s_cir2[N_DESC], s_soft, s_con, s_mag, s_snr, s_fib, s_ok;
     int stream_layout = 1;                          // experiments: bit 0 placeholder streams, bit 1 FIC work on the auxiliary stream, bit 3 the bulk drain on a stream of its own even when nothing is ingested asynchronously, bit 4 the SNR kernels on the main stream in front of the decoder (no gain: profiles/r06_step_variants.txt)

@@ -372,9 +372,14 @@ void launch_copy_f4(const void* src, void* dst, size_t n16, int blocks, hipStrea
 void launch_copy_out(const void* src_device, void* dst_host, size_t bytes, hipStream_t s);      // a kernel's stores into page-locked host memory (hipHostMalloc: the same address on the device)
 
 // Reed-Solomon (k_rs.hip)
+// The code's tables as the host uploads them once per handle (dabphy_superframes.hip: ensure_gf), in one buffer: alpha_to[256] and index_of[256] of
+// GF(256) / 0x11D (init_rs.h:48-60), then the remainder table of the generator polynomial g(x) = prod (x - alpha^i), i = 0 .. 9: row f holds the ten
+// products f g_k, k = 0 .. 9, padded to 16 bytes (rs_remainder120), then the wide pass' two counters (SfArgs::wide_stats)
+constexpr int RS_GF_BYTES = 512, RS_GTAB_BYTES = 256 * 16, RS_WIDE_STATS_OFF = RS_GF_BYTES + RS_GTAB_BYTES;
 struct RsArgs {            // contiguous superframes [n_sf][sf_stride], s = bitrate/8 codewords each
     uint8_t* data; size_t sf_stride; int n_sf, s;
     int* corr; int* uncorr;                       // [n_sf]
+    const uint8_t* gf;                            // the code's tables (above)
 };
 struct RsMscArgs {         // superframes inside a class's MSC output [n_pairs][n_cif][frame_bytes]
     uint8_t* out; int n_cif, n_pairs, frame_bytes, s, n_sf_per_pair;
@@ -382,6 +387,7 @@ struct RsMscArgs {         // superframes inside a class's MSC output [n_pairs][
     const int* first_cif;                         // [B] logical-frame slot (in this batch) where the ensemble's first superframe starts
     const int2* rows;                             // [n_pairs] rows [x, y) of the pair hold this batch's logical frames (first_valid, n_rows); x >= y: the pair is left out
     int* result;                                  // [n_pairs][n_sf_per_pair][2] = corrected symbols, uncorrectable flag
+    const uint8_t* gf;                            // the code's tables (above)
 };
 // DAB+ superframe filter (k_rs.hip: k_superframe): SuperframeFilter::Feed over the logical frames of one batch
 struct SfEvent {           // = dabphy_sf_event (include/dabphy.h)
@@ -396,12 +402,14 @@ struct SfArgs {
     SfEvent* events; int32_t* n_events;           // [n_pairs][n_cif], [n_pairs]
     uint8_t* sf; int n_slots;                     // [n_pairs][n_slots][5 * frame_bytes] corrected superframes of the synced attempts
     int32_t* stats;                               // optional [B][4]: synchronised superframes, corrected symbols, uncorrectable attempts, AUs failing their CRC
-    const uint8_t* gf;                            // alpha_to[256], index_of[256] of GF(256) / 0x11D (init_rs.h:48-60)
+    const uint8_t* gf;                            // the code's tables (above): alpha_to[256], index_of[256], the remainder table
     int32_t* accepted;                            // [n_pairs]: set by the wide pass for what it settled (nullptr: serial walk only)
     unsigned long long* wide_stats;               // [2]: pair batches the wide pass settled / was tried on
 };
 // the classes of one launch (k_rs.hip): cls = DEVICE array of n_cls argument blocks, first = DEVICE array [n_cls + 1] of first blocks
-struct SfBatch { const SfArgs* cls; const int32_t* first; int n_cls; };
+// replay (k_superframe_wide only, dabphy_time_superframe_wide): the launch is a repetition of one whose pairs have been settled since -- see the kernel
+// wide_rows (k_superframe_wide only, set by its launcher): the grid rows that have work
+struct SfBatch { const SfArgs* cls; const int32_t* first; int n_cls; int replay, wide_rows; };
 inline int sf_bucket(int frame_bytes) { const int sf_len = 5 * frame_bytes; return sf_len <= 960 ? 0 : sf_len <= 2880 ? 1 : 2; }
 // MP2 frame check (k_mp2.hip): MP2Decoder::Feed / CheckCRC over the logical frames of classic DAB services
 constexpr int MP2_RING = 8192;             // LDS ring of a service's byte stream
@@ -444,7 +452,9 @@ struct AuArgs {
     AuSvc* svc; AuRec* aus; uint2* au_src; int au_cap;           // [services], [services][au_cap] records and where their payload lies
 };
 void launch_au_pack(const AuArgs& a, int n_blocks, hipStream_t s);
-void launch_superframe_bucket(const SfBatch& Bt, int bucket, int total_blocks, int n_cif, bool wide_pass, hipStream_t s);
+// max_s: the largest s = bitrate / 8 among the launch's classes (the wide pass' work-groups hold 64 / s attempts each)
+void launch_superframe_wide(SfBatch Bt, int bucket, int total_blocks, int n_cif, int max_s, hipStream_t s);
+void launch_superframe_bucket(const SfBatch& Bt, int bucket, int total_blocks, int n_cif, int max_s, bool wide_pass, hipStream_t s);
 void launch_rs_superframes(const RsArgs& a, hipStream_t s);
 void launch_rs_msc(const RsMscArgs& a, hipStream_t s);
 

@@ -2,7 +2,43 @@
 // (split from dabphy_api.hip in round 3; dabphy_internal.h has the map of the translation units)
 #include "dabphy_internal.h"
 
+namespace {
+// The code's tables (dabphy_kernels.h: RS_GF_BYTES, RS_GTAB_BYTES), built once, thread-safely: the node receiver creates its handles from several
+// host threads.  GF(256) of RS(120,110), field polynomial 0x11D (init_rs.h:48-60): alpha_to[256], index_of[256]; then the remainder table of
+// the generator polynomial g(x) = prod (x - alpha^i), i = 0 .. 9 (init_rs.h:71-94 with fcr = 0, prim = 1): row f = f g_0 .. f g_9, zeros to 16.
+struct RsTables {
+    uint8_t b[RS_GF_BYTES + RS_GTAB_BYTES]; bool ok;
+    RsTables()
+    {
+        int sr = 1; memset(b, 0, sizeof b); b[256 + 0] = 255; b[255] = 0;
+        for (int i = 0; i < 255; i++) { b[256 + sr] = (uint8_t)i; b[i] = (uint8_t)sr; sr <<= 1; if (sr & 256) sr ^= 0x11D; sr &= 255; }
+        const uint8_t* alpha_to = b; const uint8_t* index_of = b + 256;
+        auto mul = [&](int x, int y) { return x && y ? (int)alpha_to[(index_of[x] + index_of[y]) % 255] : 0; };
+        int g[11] = {1};                                                    // g <- g (x + alpha^i), coefficient of x^k in g[k]
+        for (int i = 0; i < 10; i++) for (int k = i + 1; k >= 0; k--) g[k] = (k ? g[k - 1] : 0) ^ mul(g[k], alpha_to[i]);
+        for (int f = 0; f < 256; f++) for (int k = 0; k < 10; k++) b[RS_GF_BYTES + 16 * f + k] = (uint8_t)mul(f, g[k]);
+        // the row of f = 1 is g itself, g is monic of degree 10 and vanishes at alpha^0 .. alpha^9
+        ok = g[10] == 1;
+        for (int k = 0; k < 16; k++) ok = ok && b[RS_GF_BYTES + 16 + k] == (k < 10 ? g[k] : 0);
+        for (int i = 0; i < 10; i++) { int v = 0; for (int k = 10; k >= 0; k--) v = mul(v, alpha_to[i]) ^ g[k]; ok = ok && v == 0; }
+    }
+};
+}
+
 extern "C" {
+
+static int ensure_rs_tables(dabphy_handle* h)
+{
+    if (h->sf_gf.p) return 0;
+    static const RsTables tab;
+    if (!tab.ok) { h->err = "Reed-Solomon generator polynomial: table self-check failed"; return DABPHY_ERR_STATE; }
+    const size_t bytes = RS_WIDE_STATS_OFF + 2 * sizeof(unsigned long long);      // + the wide pass' two counters
+    int r;
+    if ((r = ensure(h, h->sf_gf, bytes))) return r;
+    HIPCHK(h, hipMemsetAsync(h->sf_gf.p, 0, bytes, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->sf_gf.p, tab.b, sizeof tab.b, hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
 
 // Device buffers of the superframe filter for F frames per batch: every DAB+-rate class gets its own region of the event / count /
 // superframe / verdict buffers (all classes of a bucket run in one launch); the window state of a class is created with the class
@@ -29,17 +65,7 @@ int prepare_superframes(dabphy_handle* h, uint32_t F)
     if ((r = ensure(h, h->sf_accept, sizeof(int32_t) * pairs))) return r;
     if ((r = ensure(h, h->sf_batch, SF_BATCH_BYTES))) return r;
     if (!h->h_sf_batch && (r = pinned_alloc(h, SF_BATCH_BYTES, &h->h_sf_batch))) return r;
-    if (!h->sf_gf.p) {
-        // GF(256) of RS(120,110), generator polynomial 0x11D (init_rs.h:48-60): alpha_to[256], index_of[256]  (built once, thread-safely:
-        // the node receiver creates its handles from several host threads)
-        struct Gf { uint8_t b[512]; Gf() { int sr = 1; memset(b, 0, sizeof b); b[256 + 0] = 255; b[255] = 0; for (int i = 0; i < 255; i++) { b[256 + sr] = (uint8_t)i; b[i] = (uint8_t)sr; sr <<= 1; if (sr & 256) sr ^= 0x11D; sr &= 255; } } };
-        static const Gf gf_tab;
-        const uint8_t (&gf)[512] = gf_tab.b;
-        if ((r = ensure(h, h->sf_gf, sizeof gf + 2 * sizeof(unsigned long long)))) return r;      // + the wide pass' two counters
-        HIPCHK(h, hipMemsetAsync(h->sf_gf.p, 0, sizeof gf + 2 * sizeof(unsigned long long), h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->sf_gf.p, gf, sizeof gf, hipMemcpyHostToDevice, h->stream));
-    }
-    return 0;
+    return ensure_rs_tables(h);
 }
 
 
@@ -51,10 +77,11 @@ int dabphy_rs_superframes(dabphy_handle* h, uint8_t* sf, uint32_t s_per_sf, uint
     int r;
     if ((r = ensure(h, h->in8, bytes))) return r;
     if ((r = ensure(h, h->rs_result, 2 * sizeof(int) * n_sf))) return r;
+    if ((r = ensure_rs_tables(h))) return r;
     HIPCHK(h, hipMemcpyAsync(h->in8.p, sf, bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(h->rs_result.p, 0, 2 * sizeof(int) * n_sf, h->stream));
     RsArgs a{}; a.data = h->in8.as<uint8_t>(); a.sf_stride = (size_t)120 * s_per_sf; a.n_sf = (int)n_sf; a.s = (int)s_per_sf;
-    a.corr = h->rs_result.as<int>(); a.uncorr = h->rs_result.as<int>() + n_sf;
+    a.corr = h->rs_result.as<int>(); a.uncorr = h->rs_result.as<int>() + n_sf; a.gf = h->sf_gf.as<uint8_t>();
     launch_rs_superframes(a, h->stream);
     HIPCHK(h, hipMemcpyAsync(sf, h->in8.p, bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(corrected, a.corr, sizeof(int) * n_sf, hipMemcpyDeviceToHost, h->stream));
@@ -70,6 +97,7 @@ int dabphy_rs_decode_msc(dabphy_handle* h, int32_t subch_index, const int32_t* f
     const int n_cif = (int)(4 * F), n_sf = n_cif / 5 + 1;
     int r;
     if ((r = ensure(h, h->rs_first, sizeof(int) * B))) return r;
+    if ((r = ensure_rs_tables(h))) return r;
     HIPCHK(h, hipMemcpyAsync(h->rs_first.p, first_cif, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
     if (corrected) memset(corrected, 0, sizeof(int32_t) * B);
     if (uncorrectable) memset(uncorrectable, 0, sizeof(int32_t) * B);
@@ -100,7 +128,7 @@ int dabphy_rs_decode_msc(dabphy_handle* h, int32_t subch_index, const int32_t* f
         HIPCHK(h, hipMemcpyAsync(h->rs_rows.p, rows.data(), P * sizeof(int2), hipMemcpyHostToDevice, h->stream));
         RsMscArgs a{}; a.out = cls.out.as<uint8_t>(); a.n_cif = n_cif; a.n_pairs = (int)P; a.pairs = cls.pair_tab.as<MscPair>();
         a.frame_bytes = cls.prot.nbits / 8; a.s = bitrate / 8; a.n_sf_per_pair = n_sf; a.rows = h->rs_rows.as<int2>();
-        a.first_cif = h->rs_first.as<int>(); a.result = h->rs_result.as<int>();
+        a.first_cif = h->rs_first.as<int>(); a.result = h->rs_result.as<int>(); a.gf = h->sf_gf.as<uint8_t>();
         if (h->profiling && first_launch) { hipError_t e = hipEventRecord(h->ev_beg[dabphy_handle::ST_RS], h->stream); (void)e; }
         launch_rs_msc(a, h->stream);
         if (h->profiling && first_launch) { hipError_t e = hipEventRecord(h->ev_end[dabphy_handle::ST_RS], h->stream); (void)e; h->ev_used[dabphy_handle::ST_RS] = true; }
@@ -139,7 +167,7 @@ static int run_superframes(dabphy_handle* h, const std::vector<SfSel>& sel, int3
     uint8_t* const hs = reinterpret_cast<uint8_t*>(h->h_sf_batch);
     uint8_t* const ds = h->sf_batch.as<uint8_t>();
     constexpr size_t BUCKET = SF_BATCH_BYTES / 3, FIRST0 = SF_BATCH_CLASSES * sizeof(SfArgs);
-    int n_in[3] = {0, 0, 0}, blocks[3] = {0, 0, 0};
+    int n_in[3] = {0, 0, 0}, blocks[3] = {0, 0, 0}, max_s[3] = {0, 0, 0};
     for (const SfSel& e : sel) {
         auto& cls = h->classes[e.cls];
         if (!cls.dabplus_rate() || cls.pairs.empty()) continue;
@@ -153,10 +181,10 @@ static int run_superframes(dabphy_handle* h, const std::vector<SfSel>& sel, int3
         a.events = h->sf_events.as<SfEvent>() + cls.sf_pair0 * n_cif; a.n_events = h->sf_count.as<int32_t>() + cls.sf_pair0;
         a.sf = h->sf_bytes.as<uint8_t>() + cls.sf_bytes0; a.n_slots = n_slots; a.stats = stats;
         a.gf = h->sf_gf.as<uint8_t>(); a.accepted = h->sf_accept.as<int32_t>() + cls.sf_pair0;
-        a.wide_stats = reinterpret_cast<unsigned long long*>(h->sf_gf.as<uint8_t>() + 512);
+        a.wide_stats = reinterpret_cast<unsigned long long*>(h->sf_gf.as<uint8_t>() + RS_WIDE_STATS_OFF);
         reinterpret_cast<SfArgs*>(hs + bk * BUCKET)[n_in[bk]] = a;
         reinterpret_cast<int32_t*>(hs + bk * BUCKET + FIRST0)[n_in[bk]] = blocks[bk];
-        n_in[bk]++; blocks[bk] += a.n_run;
+        n_in[bk]++; blocks[bk] += a.n_run; max_s[bk] = std::max(max_s[bk], a.s);
     }
     for (int bk = 0; bk < 3; bk++) {
         if (!n_in[bk]) continue;
@@ -167,8 +195,14 @@ static int run_superframes(dabphy_handle* h, const std::vector<SfSel>& sel, int3
     for (int bk = 0; bk < 3; bk++) {
         if (!n_in[bk]) continue;
         SfBatch bt{}; bt.cls = reinterpret_cast<const SfArgs*>(ds + bk * BUCKET); bt.first = reinterpret_cast<const int32_t*>(ds + bk * BUCKET + FIRST0); bt.n_cls = n_in[bk];
-        launch_superframe_bucket(bt, bk, blocks[bk], n_cif, true, st);
+        launch_superframe_bucket(bt, bk, blocks[bk], n_cif, max_s[bk], true, st);
     }
+    for (int bk = 0; bk < 3; bk++) {                                     // (dabphy_time_superframe_wide)
+        auto& w = h->sf_wide_last[bk];
+        w.bt = SfBatch{}; w.blocks = n_in[bk] ? blocks[bk] : 0; w.n_cif = n_cif; w.max_s = max_s[bk];
+        if (n_in[bk]) { w.bt.cls = reinterpret_cast<const SfArgs*>(ds + bk * BUCKET); w.bt.first = reinterpret_cast<const int32_t*>(ds + bk * BUCKET + FIRST0); w.bt.n_cls = n_in[bk]; w.bt.replay = 1; }
+    }
+    h->sf_wide_gen = h->buf_gen;
     return 0;
 }
 
@@ -352,6 +386,32 @@ int dabphy_superframes_stats(dabphy_handle* h, int32_t* stats)
     else memset(stats, 0, sf_totals_bytes(h));       // (mode 2 only: no pass was queued)
     p.totals = SfPass::EMPTY;
     return DABPHY_OK;
+}
+
+// The wide launches of the last filter pass again, alone on the device.  The pass' settle kernel has moved the windows on since, so the
+// repetition runs in the kernel's replay form: it leaves out the one attempt per pair that read frames carried INTO the batch (they are gone) and
+// the pairs that were walked, and rewrites the events and superframes of every other attempt with what they hold.
+int dabphy_time_superframe_wide(dabphy_handle* h, uint32_t iters, float* ms)
+{
+    DeviceBind dev_(h);
+    if (!h || !ms || iters == 0) return DABPHY_ERR_INVALID;
+    int r;
+    if ((r = sf_flush(h))) return r;                          // (a deferred pass that waits goes first: it is the last batch's, and it writes the staging area the launches name)
+    int total = 0;
+    for (const auto& w : h->sf_wide_last) total += w.blocks;
+    if (!total || h->sf_wide_gen != h->buf_gen) { h->err = "no superframe filter pass has run with the present buffers"; return DABPHY_ERR_STATE; }
+    HIPCHK(h, hipDeviceSynchronize());                       // alone on the device: nothing of the pipeline beside it
+    ScopedEvent e0, e1;
+    HIPCHK(h, e0.create()); HIPCHK(h, e1.create());
+    auto again = [&]() { for (int bk = 0; bk < 3; bk++) { const auto& w = h->sf_wide_last[bk]; launch_superframe_wide(w.bt, bk, w.blocks, w.n_cif, w.max_s, h->stream); } };
+    again();
+    HIPCHK(h, hipEventRecord(e0, h->stream));
+    for (uint32_t i = 0; i < iters; i++) again();
+    HIPCHK(h, hipEventRecord(e1, h->stream));
+    HIPCHK(h, hipEventSynchronize(e1));
+    float t = 0; HIPCHK(h, hipEventElapsedTime(&t, e0, e1));
+    *ms = t / iters;
+    return sync(h);
 }
 
 } // extern "C"

@@ -14,7 +14,9 @@
 // (check_rs_random); words built for the corner paths -- roots in the padding, miscorrections written in full, errors at the edges of
 // the shortened code, zero data, S0 = 0 (check_rs_directed, tests/sf_cases.py); k_rs_msc by value on the class outputs of a stream
 // (check_rs_decode_msc); the filter over the four access-unit layouts, every rejection rule and 8 .. 384 kbit/s
-// (check_superframe_layouts).  GF tables live in LDS.
+// (check_superframe_layouts); the syndromes as they are taken now -- from the word's remainder modulo the generator polynomial
+// (rs_remainder120, rs_syndromes_from_remainder) -- by an error at every position, five and six errors through the same places and the
+// corner words at 1, 8, 9 and 48 code words per superframe (tests/rs_remainder_cases.py).  The tables live in LDS.
 //
 // Second half of the file: the DAB+ superframe filter (SuperframeFilter::Feed / CheckSync, dabplus_decoder.cpp:50-213) on the
 // class output of a batch -- k_superframe_wide + k_superframe_settle (every attempt a receiver in lock makes in the batch at once,
@@ -24,7 +26,7 @@
 
 namespace dabphy {
 
-constexpr int RS_NN = 255, RS_NROOTS = 10, RS_PAD = 135, RS_A0 = 255, RS_LEN = 120;
+constexpr int RS_NN = 255, RS_NROOTS = 10, RS_PAD = 135, RS_LEN = 120;
 
 __device__ __forceinline__ int rs_modnn(int x)
 {
@@ -42,33 +44,57 @@ struct RsIo {                         // byte `pos` of codeword i
 template <typename IO>
 __device__ __forceinline__ int rs_correct120(const IO& io, const uint32_t (&syn)[RS_NROOTS], const uint8_t* __restrict__ alpha_to, const uint8_t* __restrict__ index_of, uint8_t* ws);
 
+// The syndromes S_i = c(alpha^i), i = 0 .. 9 (FCR = 0, PRIM = 1), of a received word c(x) are those of its remainder r(x) = c(x) mod g(x),
+// g(x) = prod (x - alpha^i): g(alpha^i) = 0.  A clean word -- almost every word of a receiver in lock -- has r = 0 and needs nothing else.
+// r_k = coefficient of x^k: w0 = r_0 .. r_3 (r_0 in the low byte), w1 = r_4 .. r_7, w2 = r_8 r_9
+struct RsRem {
+    uint32_t w0, w1, w2;
+    __device__ __forceinline__ bool zero() const { return (w0 | w1 | w2) == 0; }
+};
+// The division as a shift register, byte 0 (the coefficient of x^119) first: r <- r x + d - f g(x), f = r_9 the coefficient that the shift
+// moves to x^10 (g is monic).  gtab[f] = the ten products f g_k in the register's layout: one 16-byte look-up, an 80-bit shift and three
+// XORs per byte, where Horner's rule at ten roots takes twenty look-ups.
 template <typename IO>
-__device__ __forceinline__ int rs_decode120(const IO& io, const uint8_t* __restrict__ alpha_to, const uint8_t* __restrict__ index_of, uint8_t* ws)
+__device__ __forceinline__ RsRem rs_remainder120(const IO& io, const uint4* __restrict__ gtab)
 {
-    // the syndromes of the common case live in registers: `syn` is only ever indexed by unrolled constants (the array the
-    // Berlekamp-Massey iteration indexes dynamically is a copy made on the error path -- sharing one array sent every
-    // Horner step through scratch memory, 10x slower)
-    uint32_t syn[RS_NROOTS];
-    {
-        const uint32_t d0 = io.get(0);
-#pragma unroll
-        for (int i = 0; i < RS_NROOTS; i++) syn[i] = d0;
+    RsRem r{0, 0, 0};
+#pragma unroll 4
+    for (int j = 0; j < RS_LEN; j++) {
+        const uint4 g = gtab[r.w2 >> 8];
+        const uint32_t d = io.get(j);
+        r.w2 = (((r.w2 << 8) | (r.w1 >> 24)) & 0xFFFFu) ^ g.z;
+        r.w1 = ((r.w1 << 8) | (r.w0 >> 24)) ^ g.y;
+        r.w0 = ((r.w0 << 8) | d) ^ g.x;
     }
-#pragma unroll 2
-    for (int j = 1; j < RS_LEN; j++) {
-        const uint32_t dj = io.get(j);
+    return r;
+}
+// S_i = r(alpha^i) = XOR_k r_k alpha^(i k): ten terms per root.  Only for r != 0; `syn` is only ever indexed by unrolled constants (the
+// array the Berlekamp-Massey iteration indexes dynamically is a copy made in rs_correct120 -- sharing one array sent it through scratch memory)
+__device__ __forceinline__ void rs_syndromes_from_remainder(const RsRem& r, uint32_t (&syn)[RS_NROOTS], const uint8_t* __restrict__ alpha_to, const uint8_t* __restrict__ index_of)
+{
 #pragma unroll
-        for (int i = 0; i < RS_NROOTS; i++)
-        {
-            // FCR = 0, PRIM = 1.  index_of[..] + i <= 254 + 9, where modnn() is one conditional subtraction: written
-            // branch-free so that the ten Horner chains overlap their two table look-ups instead of queueing behind ten loops
-            // Both look-ups are unconditional (index_of[0] = 255 is harmless, its result is discarded by the select): a
-            // look-up under `if (syn != 0)` is a branch per syndrome, ten serial round trips to LDS per byte.
-            const uint32_t e = index_of[syn[i]] + i;
-            const uint32_t a = alpha_to[e >= RS_NN ? e - RS_NN : e];
-            syn[i] = (syn[i] == 0) ? dj : (dj ^ a);
+    for (int i = 0; i < RS_NROOTS; i++) syn[i] = 0;
+#pragma unroll
+    for (int k = 0; k < RS_NROOTS; k++) {
+        const uint32_t rk = ((k < 4 ? r.w0 : k < 8 ? r.w1 : r.w2) >> (8 * (k & 3))) & 255u;
+        uint32_t ex = index_of[rk];                                      // 255 for r_k = 0: the terms are masked below
+        syn[0] ^= rk;
+#pragma unroll
+        for (int i = 1; i < RS_NROOTS; i++) {
+            ex += (uint32_t)k; ex = ex >= RS_NN ? ex - RS_NN : ex;
+            const uint32_t av = alpha_to[ex >= RS_NN ? ex - RS_NN : ex];
+            syn[i] ^= rk ? av : 0u;
         }
     }
+}
+
+template <typename IO>
+__device__ __forceinline__ int rs_decode120(const IO& io, const uint8_t* __restrict__ alpha_to, const uint8_t* __restrict__ index_of, const uint4* __restrict__ gtab, uint8_t* ws)
+{
+    const RsRem r = rs_remainder120(io, gtab);
+    if (r.zero()) return 0;
+    uint32_t syn[RS_NROOTS];
+    rs_syndromes_from_remainder(r, syn, alpha_to, index_of);
     return rs_correct120(io, syn, alpha_to, index_of, ws);
 }
 
@@ -176,32 +202,38 @@ __device__ __forceinline__ int rs_correct120(const IO& io, const uint32_t (&syn_
     return count;
 }
 
-__device__ __forceinline__ void rs_tables(uint8_t* alpha_to, uint8_t* index_of, int t, int nthreads)
+// The code's tables from the copy the host uploaded (RS_GF_BYTES + RS_GTAB_BYTES at gf) into LDS; gtab = nullptr: the GF tables only.
+// The callers' barrier follows.
+// (NT threads, NT >= 64 dividing 256.  Every load is issued before the first store: a loop of load-then-store waits out one round trip
+// to memory per turn, which is what a work-group of one wave spends its time on)
+template <int NT>
+__device__ __forceinline__ void rs_tables(const uint8_t* __restrict__ gf, uint8_t* alpha_to, uint8_t* index_of, uint4* gtab, int t)
 {
-    if (t == 0) {                                              // init_rs.h:48-60
-        int sr = 1;
-        index_of[0] = RS_A0; alpha_to[RS_A0] = 0;
-        for (int i = 0; i < RS_NN; i++) {
-            index_of[sr] = (uint8_t)i; alpha_to[i] = (uint8_t)sr;
-            sr <<= 1; if (sr & 256) sr ^= 0x11D; sr &= RS_NN;
-        }
-    }
-    (void)nthreads;
-    __syncthreads();
+    constexpr int PER = RS_GTAB_BYTES / 16 / NT;                            // 4 or 1 (named registers: an array of them went through scratch memory)
+    static_assert(PER == 1 || PER == 4, "64 or 256 threads");
+    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(gf + RS_GF_BYTES) + t;
+    uint32_t a = 0, b = 0;
+    uint4 g0{}, g1{}, g2{}, g3{};
+    if (t < 64) { a = reinterpret_cast<const uint32_t*>(gf)[t]; b = reinterpret_cast<const uint32_t*>(gf + 256)[t]; }
+    if (gtab) { g0 = src[0]; if (PER == 4) { g1 = src[NT]; g2 = src[2 * NT]; g3 = src[3 * NT]; } }
+    if (t < 64) { reinterpret_cast<uint32_t*>(alpha_to)[t] = a; reinterpret_cast<uint32_t*>(index_of)[t] = b; }
+    if (gtab) { gtab[t] = g0; if (PER == 4) { gtab[NT + t] = g1; gtab[2 * NT + t] = g2; gtab[3 * NT + t] = g3; } }
 }
 
 // Contiguous superframes: sf[n_sf][120*s]; result per superframe: corrected-symbol total and uncorrectable flag.
 __global__ void __launch_bounds__(256) k_rs_superframes(RsArgs A)
 {
-    __shared__ uint8_t alpha_to[256], index_of[256];
+    __shared__ __attribute__((aligned(16))) uint8_t alpha_to[256], index_of[256];
+    __shared__ uint4 gtab[RS_GTAB_BYTES / 16];
     __shared__ uint8_t ws[256 * RS_WS_BYTES];
-    rs_tables(alpha_to, index_of, threadIdx.x, blockDim.x);
+    rs_tables<256>(A.gf, alpha_to, index_of, gtab, threadIdx.x);
+    __syncthreads();
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int total = A.n_sf * A.s;
     if (idx >= total) return;
     const int sf = idx / A.s, i = idx % A.s;
     RsIo io; io.base = A.data + (size_t)sf * A.sf_stride + i; io.pos_stride = (size_t)A.s;
-    const int c = rs_decode120(io, alpha_to, index_of, ws + threadIdx.x * RS_WS_BYTES);
+    const int c = rs_decode120(io, alpha_to, index_of, gtab, ws + threadIdx.x * RS_WS_BYTES);
     if (c < 0) atomicOr(A.uncorr + sf, 1);
     else if (c > 0) atomicAdd(A.corr + sf, c);
 }
@@ -217,9 +249,11 @@ struct RsMscIo {
 
 __global__ void __launch_bounds__(256) k_rs_msc(RsMscArgs A)
 {
-    __shared__ uint8_t alpha_to[256], index_of[256];
+    __shared__ __attribute__((aligned(16))) uint8_t alpha_to[256], index_of[256];
+    __shared__ uint4 gtab[RS_GTAB_BYTES / 16];
     __shared__ uint8_t ws[256 * RS_WS_BYTES];
-    rs_tables(alpha_to, index_of, threadIdx.x, blockDim.x);
+    rs_tables<256>(A.gf, alpha_to, index_of, gtab, threadIdx.x);
+    __syncthreads();
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int per_pair = A.n_sf_per_pair * A.s;
     if (idx >= A.n_pairs * per_pair) return;
@@ -233,8 +267,8 @@ __global__ void __launch_bounds__(256) k_rs_msc(RsMscArgs A)
     RsMscIo io;
     io.frame_bytes = A.frame_bytes; io.s = A.s; io.i = i; io.frame_stride = (size_t)A.frame_bytes;
     io.frames = A.out + ((size_t)pair * A.n_cif + r0) * A.frame_bytes;
-    const int c = rs_decode120(io, alpha_to, index_of, ws + threadIdx.x * RS_WS_BYTES);
-    int* cnt = A.result + 2 * ((size_t)pair * A.n_sf_per_pair + q);
+    const int c = rs_decode120(io, alpha_to, index_of, gtab, ws + threadIdx.x * RS_WS_BYTES);
+    int* cnt =A.result + 2 * ((size_t)pair * A.n_sf_per_pair + q);
     if (c < 0) atomicOr(cnt + 1, 1);
     else if (c > 0) atomicAdd(cnt, c);
 }
@@ -266,10 +300,9 @@ __device__ __forceinline__ uint16_t crc16_msb_tab(const uint8_t* data, int len, 
 constexpr int SF_PREFETCH = 6;      // rows of the class output in flight per work-group (serial walk)
 
 // GF(256) tables of the code (init_rs.h:48-60) from the copy the host uploaded, and the byte-wise table of CRC-16-CCITT (0x1021)
-__device__ __forceinline__ void sf_tables(const SfArgs& A, uint8_t* alpha_to, uint8_t* index_of, uint16_t* crctab, int t)
+__device__ __forceinline__ void sf_tables(const SfArgs& A, uint8_t* alpha_to, uint8_t* index_of, uint4* gtab, uint16_t* crctab, int t)
 {
-    reinterpret_cast<uint32_t*>(alpha_to)[t] = reinterpret_cast<const uint32_t*>(A.gf)[t];
-    reinterpret_cast<uint32_t*>(index_of)[t] = reinterpret_cast<const uint32_t*>(A.gf + 256)[t];
+    rs_tables<64>(A.gf, alpha_to, index_of, gtab, t);
     if (crctab)
         for (int v = t; v < 256; v += 64) {
             uint16_t c = (uint16_t)(v << 8);
@@ -284,14 +317,19 @@ __device__ __forceinline__ void sf_tables(const SfArgs& A, uint8_t* alpha_to, ui
 // frame number of the batch, whatever slots the demodulated frames occupied; frames before the 16-CIF fill of the time de-interleaver,
 // dab-audio.cpp:146-149, counted from the CIF at which the pair was selected (MscPair::cif0), are never emitted).  If every attempt synchronises, attempts happen at frames 5q + 4 of that sequence: nq of them.
 struct SfPlan { int fc, cu, n_rows, r_first, avail, nq; };
-__device__ __forceinline__ SfPlan sf_plan(const SfArgs& A, const MscPair& pp, const uint8_t* st)
+// (called by all 64 lanes of the work-group's wave together: lane t looks at frame t, t + 64, ... -- one round trip to memory for the batch's
+// descriptors where a loop over the frames makes one per frame)
+__device__ __forceinline__ SfPlan sf_plan(const SfArgs& A, const MscPair& pp, const uint8_t* st, int t)
 {
     const int b = pp.ens;
     SfPlan p;
     p.fc = *reinterpret_cast<const int32_t*>(st);
     p.cu = p.fc == 5 ? 4 : p.fc;
     int nv = 0;
-    for (int f = 0; f < A.n_frames; f++) nv += A.desc[(size_t)b * A.n_frames + f].valid == 1 ? 1 : 0;
+    for (int f0 = 0; f0 < A.n_frames; f0 += 64) {
+        const int f = f0 + t;
+        nv += __popcll(__ballot(f < A.n_frames && A.desc[(size_t)b * A.n_frames + (f < A.n_frames ? f : 0)].valid == 1));
+    }
     const long long c0 = 4 * A.desc[(size_t)b * A.n_frames].frame_no;
     p.n_rows = 4 * nv;
     p.r_first = 0;
@@ -301,15 +339,32 @@ __device__ __forceinline__ SfPlan sf_plan(const SfArgs& A, const MscPair& pp, co
     return p;
 }
 
-// One attempt on the 5-frame copy in s_sf: Reed-Solomon over its s code words, then CheckSync (dabplus_decoder.cpp:97-213).
-// Thread 0 gets the attempt's event (cif and sf_slot are the caller's); sh.sync / corr / unc are valid for all threads on return.
-struct SfShared { int corr, unc, sync, au_start[8]; };
-__device__ __forceinline__ void sf_attempt(uint8_t* s_sf, int fb, int s, const uint8_t* alpha_to, const uint8_t* index_of, uint8_t* s_ws,
-                                           SfShared& sh, SfEvent& e, int t)
+// Reed-Solomon over the s code words of each of the attempts a_first .. n_att - 1, 5-frame copies sf_len bytes apart in s_sf (dabplus_decoder.cpp:97), by the 64
+// lanes of one wave; corr[a] / unc[a] (LDS, zeroed here) = the attempt's corrected symbols / whether a word was given up, valid for all
+// threads on return.  Two forms, the caller's choice:
+//   SPLIT = false  every lane owns a code word (attempt t / s, word t % s; n_att s <= 64) and divides it by the generator polynomial:
+//                  120 dependent steps of one look-up each, and nothing more for a clean word.  64 code words per wave: the wide pass.
+//                  gtab = the remainder table in LDS, s_ws = 64 workspaces.
+//   SPLIT = true   a_first = 0, n_att = 1, eight code words at a time with the whole wave, each word's positions split over eight lanes: 15 independent
+//                  steps per lane.  The serial walk makes one attempt at a time on one wave and at most 48 code words would leave its lanes
+//                  idle through 120 dependent steps: it keeps this form.  gtab unused, s_ws = 8 workspaces.
+// Both hand rs_correct120 the same syndromes.
+template <bool SPLIT>
+__device__ __forceinline__ void sf_rs_words(uint8_t* s_sf, int sf_len, int s, int a_first, int n_att, const uint8_t* alpha_to, const uint8_t* index_of, const uint4* gtab,
+                                            uint8_t* s_ws, int* corr, int* unc, int t)
 {
-    const int sf_len = 5 * fb;
-    if (t == 0) { sh.corr = 0; sh.unc = 0; }
+    if (t < n_att) { corr[t] = 0; unc[t] = 0; }
     __syncthreads();
+    if (!SPLIT) {
+        const int a = t / s, c = t - a * s;
+        if (a >= a_first && a < n_att) {
+            RsIo io; io.base = s_sf + a * sf_len + c; io.pos_stride = (size_t)s;
+            const int n = rs_decode120(io, alpha_to, index_of, gtab, s_ws + t * RS_WS_BYTES);
+            if (n < 0) atomicOr(&unc[a], 1); else if (n > 0) atomicAdd(&corr[a], n);
+        }
+        __syncthreads();
+        return;
+    }
     // Syndromes, eight codewords at a time with the whole wave: S_i = XOR_j d_j alpha^(i (119 - j)) is a sum, so lane
     // (codeword c = l & 7, byte group l >> 3 = 15 positions) adds its terms without any chain of dependent look-ups and
     // three butterfly exchanges fold the eight groups (Horner's 119 dependent steps were the whole cost of this kernel).
@@ -341,33 +396,51 @@ __device__ __forceinline__ void sf_attempt(uint8_t* s_sf, int fb, int s, const u
         if (jg == 0 && c < s) {
             RsIo io; io.base = s_sf + c; io.pos_stride = (size_t)s;
             const int n = rs_correct120(io, syn, alpha_to, index_of, s_ws + (t & 7) * RS_WS_BYTES);
-            if (n < 0) atomicOr(&sh.unc, 1); else if (n > 0) atomicAdd(&sh.corr, n);
+            if (n < 0) atomicOr(&unc[0], 1); else if (n > 0) atomicAdd(&corr[0], n);
         }
     }
     __syncthreads();
-    if (t == 0) {                                                          // CheckSync, :160-213
-        const uint8_t* sf = s_sf;
-        int sync = 0, num_aus = 0;
-        if (!(sf[3] == 0x00 && sf[4] == 0x00) && (uint16_t)(sf[0] << 8 | sf[1]) == crc16_msb(sf + 2, 9, false, false, 0x782F)) {
-            const int dac_rate = sf[2] & 0x40, sbr_flag = sf[2] & 0x20;
-            num_aus = dac_rate ? (sbr_flag ? 3 : 6) : (sbr_flag ? 2 : 4);
-            sh.au_start[0] = dac_rate ? (sbr_flag ? 6 : 11) : (sbr_flag ? 5 : 8);
-            sh.au_start[num_aus] = sf_len / 120 * 110;
-            sh.au_start[1] = sf[3] << 4 | sf[4] >> 4;
-            if (num_aus >= 3) sh.au_start[2] = (sf[4] & 0x0F) << 8 | sf[5];
-            if (num_aus >= 4) sh.au_start[3] = sf[6] << 4 | sf[7] >> 4;
-            if (num_aus == 6) { sh.au_start[4] = (sf[7] & 0x0F) << 8 | sf[8]; sh.au_start[5] = sf[9] << 4 | sf[10] >> 4; }
-            sync = 1;
-            for (int i = 0; i < num_aus; i++) if (sh.au_start[i] >= sh.au_start[i + 1]) sync = 0;
-        }
-        sh.sync = sync;
-        e = SfEvent{};
-        e.corrected = sh.corr; e.uncorrectable = sh.unc; e.sync = sync; e.sf_slot = -1;
-        if (sync) {
-            e.format = sf[2]; e.num_aus = num_aus;
-            for (int i = 0; i <= num_aus; i++) e.au_start[i] = sh.au_start[i];
-        }
+}
+
+// CheckSync (dabplus_decoder.cpp:160-213) of one corrected superframe by ONE lane -> the attempt's event (cif and sf_slot are the caller's).
+// Everything is indexed by unrolled constants: the lane keeps the start table in registers.
+__device__ __forceinline__ int sf_check_sync(const uint8_t* sf, int sf_len, int corr, int unc, SfEvent& e)
+{
+    int sync = 0, num_aus = 0;
+    int au[7] = {0, 0, 0, 0, 0, 0, 0};
+    if (!(sf[3] == 0x00 && sf[4] == 0x00) && (uint16_t)(sf[0] << 8 | sf[1]) == crc16_msb(sf + 2, 9, false, false, 0x782F)) {
+        const int dac_rate = sf[2] & 0x40, sbr_flag = sf[2] & 0x20;
+        num_aus = dac_rate ? (sbr_flag ? 3 : 6) : (sbr_flag ? 2 : 4);
+        au[0] = dac_rate ? (sbr_flag ? 6 : 11) : (sbr_flag ? 5 : 8);
+        au[1] = sf[3] << 4 | sf[4] >> 4;
+        au[2] = (sf[4] & 0x0F) << 8 | sf[5];
+        au[3] = sf[6] << 4 | sf[7] >> 4;
+        au[4] = (sf[7] & 0x0F) << 8 | sf[8];
+        au[5] = sf[9] << 4 | sf[10] >> 4;
+        sync = 1;
+#pragma unroll
+        for (int i = 1; i < 7; i++) au[i] = i < num_aus ? au[i] : i == num_aus ? sf_len / 120 * 110 : 0;
+#pragma unroll
+        for (int i = 0; i < 6; i++) if (i < num_aus && au[i] >= au[i + 1]) sync = 0;
     }
+    e = SfEvent{};
+    e.corrected = corr; e.uncorrectable = unc; e.sync = sync; e.sf_slot = -1;
+    if (sync) {
+        e.format = sf[2]; e.num_aus = num_aus;
+#pragma unroll
+        for (int i = 0; i < 7; i++) e.au_start[i] = au[i];
+    }
+    return sync;
+}
+
+// One attempt of the serial walk on the 5-frame copy in s_sf: Reed-Solomon over its s code words, then CheckSync.
+// Thread 0 gets the attempt's event; sh.sync / corr / unc are valid for all threads on return.
+struct SfShared { int corr, unc, sync; };
+__device__ __forceinline__ void sf_attempt(uint8_t* s_sf, int fb, int s, const uint8_t* alpha_to, const uint8_t* index_of, uint8_t* s_ws,
+                                           SfShared& sh, SfEvent& e, int t)
+{
+    sf_rs_words<true>(s_sf, 5 * fb, s, 0, 1, alpha_to, index_of, nullptr, s_ws, &sh.corr, &sh.unc, t);
+    if (t == 0) sh.sync = sf_check_sync(s_sf, 5 * fb, sh.corr, sh.unc, e);
     __syncthreads();
 }
 
@@ -387,6 +460,18 @@ __device__ __forceinline__ void sf_au_crcs(const SfArgs& A, SfEvent* ev, size_t 
             if (au_len >= 2 && (uint16_t)(au[au_len - 2] << 8 | au[au_len - 1]) == crc16_msb_tab(au, au_len - 2, true, true, crctab)) atomicOr(&ev[e_i].au_crc_ok, 1 << au_i);
             else atomicAdd(aubad, 1);
         }
+    }
+}
+
+// n 8-byte words from memory into LDS by one wave, up to 16 loads of a lane in flight (see rs_tables)
+__device__ __forceinline__ void sf_copy_in(uint2* dst, const uint2* __restrict__ src, int n, int t)
+{
+    for (int base = 0; base < n; base += 16 * 64) {
+        uint2 v[16];
+#pragma unroll
+        for (int u = 0; u < 16; u++) { const int i = base + u * 64 + t; v[u] = i < n ? src[i] : uint2{0, 0}; }
+#pragma unroll
+        for (int u = 0; u < 16; u++) { const int i = base + u * 64 + t; if (i < n) dst[i] = v[u]; }
     }
 }
 
@@ -413,38 +498,75 @@ __device__ __forceinline__ SfArgs sf_args_of(const SfBatch& Bt, uint32_t& bx)
     return a;
 }
 
-template <int SF_MAX>
+// A work-group takes as many consecutive attempts of its pair as fill its 64 lanes with code words: 64 / s of them (eight at 64 kbit/s, one
+// above 256 kbit/s; s <= 48), blockIdx.y = which ones.  Their windows are 64 / s * 120 s <= 7680 bytes of LDS whatever the bit rate; the
+// buckets' instances differ in the attempts a work-group can hold (64 / 7 / 2: s >= 1 / 9 / 25).  The launch keeps its grid of one row per
+// attempt of the batch -- the queue-order records (tests/queue_order) pin the launches of dabphy_process, grids included --; the rows behind
+// the Bt.wide_rows that have work for the launch's largest s return before they touch memory (the heavy rows are dispatched first; measured:
+// profiles/sf_wide_remainder.txt).  Once per work-group instead of once per attempt: the class's argument block, sf_plan (a descriptor per frame
+// of the batch) and the tables.  Consecutive attempts read consecutive frames: one coalesced copy (two where attempt 0 starts in the carried
+// frames of the state), and one copy out when all of them synchronise.
+// Bt.replay (dabphy_time_superframe_wide): the launch repeats the pass of a batch that k_superframe_settle has settled since -- the state holds the
+// frames carried OUT of the batch, no longer those carried in.  How many were carried in follows from the first event's row; the attempt
+// that read them is left out (its event and superframe stay), every other attempt rewrites what it wrote.  Pairs that were walked are left out.
+constexpr int SF_WIDE_LANES = 64, SF_WIDE_LDS = SF_WIDE_LANES * RS_LEN;
+template <int SF_MAX>       // superframe bytes of the bucket (120 s)
 __global__ void __launch_bounds__(64) k_superframe_wide(SfBatch Bt)
 {
+    if ((int)blockIdx.y >= Bt.wide_rows) return;
+    constexpr int MAX_ATT = SF_MAX <= 960 ? SF_WIDE_LANES : SF_MAX <= 2880 ? SF_WIDE_LANES / 9 : SF_WIDE_LANES / 25;
     uint32_t bx = blockIdx.x;
     const SfArgs A = sf_args_of(Bt, bx);
-    __shared__ __attribute__((aligned(16))) uint8_t s_sf[SF_MAX];
+    __shared__ __attribute__((aligned(16))) uint8_t s_sf[SF_WIDE_LDS];
     __shared__ __attribute__((aligned(16))) uint8_t alpha_to[256], index_of[256];
-    __shared__ SfShared sh;
-    __shared__ uint8_t s_ws[8 * RS_WS_BYTES];
-    const int t = threadIdx.x, q = (int)blockIdx.y;
+    __shared__ uint4 s_gtab[RS_GTAB_BYTES / 16];
+    __shared__ int s_corr[MAX_ATT], s_unc[MAX_ATT], s_sync[MAX_ATT];
+    __shared__ uint8_t s_ws[SF_WIDE_LANES * RS_WS_BYTES];       // error-path workspaces, one per code-word lane
+    const int t = threadIdx.x, s = A.s;
     const int fb = A.frame_bytes, sf_len = 5 * fb, fw = fb >> 3;
+    const int per_group = SF_WIDE_LANES / s < MAX_ATT ? SF_WIDE_LANES / s : MAX_ATT;
+    const int q0 = (int)blockIdx.y * per_group;                   // the work-group's first attempt
     const size_t bm = A.run ? (size_t)A.run[bx] : (size_t)bx;      // the pair
     const uint8_t* st = A.state + bm * A.state_stride;
-    const SfPlan p = sf_plan(A, A.pairs[bm], st);
-    if (q >= p.nq) return;
-    sf_tables(A, alpha_to, index_of, nullptr, t);
-    for (int k = 0; k < 5; k++) {
-        const int g = 5 * q + k;                                               // frame g of (carried frames, then rows)
-        const uint8_t* src = g < p.cu ? st + 16 + (size_t)(p.fc - p.cu + g) * fb : A.out + (bm * A.n_cif + (p.r_first + g - p.cu)) * fb;
-        for (int i = t; i < fw; i += 64) reinterpret_cast<uint2*>(s_sf + k * fb)[i] = reinterpret_cast<const uint2*>(src)[i];
+    SfPlan p = sf_plan(A, A.pairs[bm], st, t);
+    int q_first = 0;
+    if (Bt.replay) {
+        if (!A.accepted[bm] || A.n_events[bm] < 1) return;
+        const int cu = p.r_first + 4 - A.events[bm * A.n_cif].cif;
+        if (cu < 0 || cu > 4) return;
+        p.fc = p.cu = cu; p.nq = p.avail > 0 ? (cu + p.avail) / 5 : 0;
+        q_first = cu > 0;
     }
-    SfEvent e;
-    sf_attempt(s_sf, fb, A.s, alpha_to, index_of, s_ws, sh, e, t);
-    if (t == 0) {
+    if (q0 >= p.nq) return;
+    const int na = p.nq - q0 < per_group ? p.nq - q0 : per_group;
+    sf_tables(A, alpha_to, index_of, s_gtab, nullptr, t);
+    {
+        // frames 5 q0 .. 5 (q0 + na) of (carried frames, then rows): the first n_st from the state, the rest consecutive rows of the class output
+        const int g0 = 5 * q0, ng = 5 * na;
+        const int n_st = p.cu - g0 <= 0 ? 0 : p.cu - g0 < ng ? p.cu - g0 : ng;
+        if (n_st) sf_copy_in(reinterpret_cast<uint2*>(s_sf), reinterpret_cast<const uint2*>(st + 16 + (size_t)(p.fc - p.cu + g0) * fb), n_st * fw, t);
+        sf_copy_in(reinterpret_cast<uint2*>(s_sf + n_st * fb), reinterpret_cast<const uint2*>(A.out + (bm * A.n_cif + (p.r_first + g0 + n_st - p.cu)) * fb), (ng - n_st) * fw, t);
+    }
+    sf_rs_words<false>(s_sf, sf_len, s, q0 < q_first, na, alpha_to, index_of, s_gtab, s_ws, s_corr, s_unc, t);
+    if (t < na) {                                                              // one lane per attempt
+        const int q = q0 + t;
+        SfEvent e;
+        const int sync = sf_check_sync(s_sf + t * sf_len, sf_len, s_corr[t], s_unc[t], e);
         e.cif = p.r_first + 5 * q + 4 - p.cu;                                  // the row whose arrival triggers the attempt
-        if (sh.sync) e.sf_slot = q;
-        A.events[bm * A.n_cif + q] = e;
+        if (sync) e.sf_slot = q;
+        s_sync[t] = sync && q >= q_first;
+        if (q >= q_first) A.events[bm * A.n_cif + q] = e;
     }
-    if (sh.sync) {
-        uint8_t* gsf = A.sf + (bm * A.n_slots + q) * sf_len;
-        for (int i = t; i < 5 * fw; i += 64) reinterpret_cast<uint2*>(gsf)[i] = reinterpret_cast<const uint2*>(s_sf)[i];
-    }
+    __syncthreads();
+    int n_sync = 0;
+    for (int a = 0; a < na; a++) n_sync += s_sync[a];
+    uint8_t* gsf = A.sf + (bm * A.n_slots + q0) * sf_len;                       // (slot = attempt: consecutive)
+    if (n_sync == na)
+        for (int i = t; i < na * 5 * fw; i += 64) reinterpret_cast<uint2*>(gsf)[i] = reinterpret_cast<const uint2*>(s_sf)[i];
+    else
+        for (int a = 0; a < na; a++)
+            if (s_sync[a])
+                for (int i = t; i < 5 * fw; i += 64) reinterpret_cast<uint2*>(gsf + (size_t)a * sf_len)[i] = reinterpret_cast<const uint2*>(s_sf + a * sf_len)[i];
 }
 
 __global__ void __launch_bounds__(64) k_superframe_settle(SfBatch Bt)
@@ -458,7 +580,7 @@ __global__ void __launch_bounds__(64) k_superframe_settle(SfBatch Bt)
     const size_t bm = A.run ? (size_t)A.run[bx] : (size_t)bx;      // the pair
     const int b = A.pairs[bm].ens;
     uint8_t* st = A.state + bm * A.state_stride;
-    const SfPlan p = sf_plan(A, A.pairs[bm], st);
+    const SfPlan p = sf_plan(A, A.pairs[bm], st, t);
     SfEvent* ev = A.events + bm * A.n_cif;
     for (int v = t; v < 256; v += 64) {
         uint16_t c = (uint16_t)(v << 8);
@@ -508,13 +630,13 @@ __global__ void __launch_bounds__(64, SF_MAX <= 2880 ? 4 : 2) k_superframe(SfBat
     const size_t bm = A.run ? (size_t)A.run[bx] : (size_t)bx;      // the pair
     const int b = A.pairs[bm].ens;
     if (A.accepted && A.accepted[bm]) return;                  // settled by the wide pass
-    sf_tables(A, alpha_to, index_of, s_crctab, t);
+    sf_tables(A, alpha_to, index_of, nullptr, s_crctab, t);
     if (t == 0) s_aubad = 0;
     const int fb = A.frame_bytes, sf_len = 5 * fb;
     uint8_t* const s_raw = s_dyn;
     uint8_t* const s_sf = s_dyn + SF_MAX;
     uint8_t* st = A.state + bm * A.state_stride;
-    const SfPlan p = sf_plan(A, A.pairs[bm], st);
+    const SfPlan p = sf_plan(A, A.pairs[bm], st, t);
     int frame_count = p.fc;
     __syncthreads();
     for (int i = t; i < frame_count * fb; i += 64) s_raw[i] = st[16 + i];     // carried frames, oldest first
@@ -587,16 +709,26 @@ __global__ void __launch_bounds__(64, SF_MAX <= 2880 ? 4 : 2) k_superframe(SfBat
 
 // bucket = index of the kernels' LDS size (superframes of <= 960 / <= 2880 / <= 5760 bytes: <= 64 / 192 / 384 kbit/s); Bt.cls are the
 // classes of that bucket (DEVICE array), total_blocks = Bt.first[n_cls] (known to the host), n_cif = CIFs per batch, wide = run the wide pass
-void launch_superframe_bucket(const SfBatch& Bt, int bucket, int total_blocks, int n_cif, bool wide_pass, hipStream_t s)
+// the wide pass alone: a grid row per attempt of the batch, (n_cif + 4) / 5, of which the first wide_rows have work: 64 / s attempts per
+// work-group, counted for the launch's largest s (the surplus work-groups of classes with a smaller one leave once they have their plan)
+void launch_superframe_wide(SfBatch Bt, int bucket, int total_blocks, int n_cif, int max_s, hipStream_t s)
+{
+    if (total_blocks <= 0 || max_s < 1 || max_s > SF_WIDE_LANES) return;
+    const int per_group = SF_WIDE_LANES / max_s, attempts = (n_cif + 4) / 5;
+    Bt.wide_rows = (attempts + per_group - 1) / per_group;
+    const dim3 wide(total_blocks, attempts);
+    if (bucket == 0) hipLaunchKernelGGL(k_superframe_wide<960>, wide, dim3(64), 0, s, Bt);
+    else if (bucket == 1) hipLaunchKernelGGL(k_superframe_wide<2880>, wide, dim3(64), 0, s, Bt);
+    else hipLaunchKernelGGL(k_superframe_wide<5760>, wide, dim3(64), 0, s, Bt);
+}
+
+void launch_superframe_bucket(const SfBatch& Bt, int bucket, int total_blocks, int n_cif, int max_s, bool wide_pass, hipStream_t s)
 {
     if (total_blocks <= 0) return;
     const dim3 grid(total_blocks);
     if (wide_pass) {
         // the wide pass: every attempt a locked receiver makes in this batch at once, then the verdict per (ensemble, sub-channel) pair
-        const dim3 wide(grid.x, (n_cif + 4) / 5);
-        if (bucket == 0) hipLaunchKernelGGL(k_superframe_wide<960>, wide, dim3(64), 0, s, Bt);
-        else if (bucket == 1) hipLaunchKernelGGL(k_superframe_wide<2880>, wide, dim3(64), 0, s, Bt);
-        else hipLaunchKernelGGL(k_superframe_wide<5760>, wide, dim3(64), 0, s, Bt);
+        launch_superframe_wide(Bt, bucket, total_blocks, n_cif, max_s, s);
         hipLaunchKernelGGL(k_superframe_settle, grid, dim3(64), 0, s, Bt);
     }
     if (bucket == 0) hipLaunchKernelGGL(k_superframe<960>, grid, dim3(64), 0, s, Bt);            // <= 64 kbit/s
