@@ -1019,8 +1019,22 @@ static void rx_get_samples(rx_t* r, orc_cf32* v, int n, int32_t phase)
     }
 }
 
+/* the optional trace of the acquisition head (dabphy_oracle.h); returns the event's values, or NULL when it is not kept */
+typedef struct { int32_t* kind; int64_t* val; int cap, n; } rx_trace_t;
+static int64_t* rx_trace(rx_trace_t* io, int kind, int64_t v0, int64_t v1, int64_t v2, int64_t v3, int64_t v4)
+{
+    int64_t* v = NULL;
+    if (io->kind && io->val && io->n < io->cap) {
+        io->kind[io->n] = kind;
+        v = io->val + (size_t)ORC_TR_VALS * io->n;
+        v[0] = v0; v[1] = v1; v[2] = v2; v[3] = v3; v[4] = v4; v[5] = v[6] = v[7] = 0;
+    }
+    io->n++;
+    return v;
+}
+
 /* ofdm-processor.cpp:235-501 + lock-step hand-over to ofdm-decoder.cpp:93-130, fic-handler, msc-handler.cpp:129-158 */
-int orc_receiver_run(orc_run_io* io)
+static int receiver_run(orc_run_io* io, rx_trace_t* tr)
 {
     orc_init();
     rx_t R; memset(&R, 0, sizeof R);
@@ -1037,12 +1051,13 @@ int orc_receiver_run(orc_run_io* io)
     int fic_ratio = 0;
     int frame = 0;
     float currentStrength; int syncBufferIndex, counter; int32_t startIndex;
+    int cause = ORC_CAUSE_PRIMED; int64_t entry_pos;
     io->n_fib = io->n_frames = io->n_snr = io->n_sync_true = io->n_sync_false = io->n_cir = 0;
 
     R.sLevel = 0;
     for (int i = 0; i < ORC_TF / 2; i++) { rx_get_sample(&R, 0); if (R.failed) goto done; }
 notSynced:
-    syncBufferIndex = 0; currentStrength = 0;
+    syncBufferIndex = 0; currentStrength = 0; entry_pos = R.pos;
     for (int i = 0; i < 50; i++) {
         orc_cf32 s = rx_get_sample(&R, 0); if (R.failed) goto done;
         envBuffer[syncBufferIndex] = l1_norm(s);
@@ -1051,14 +1066,16 @@ notSynced:
     }
     counter = 0;
     io->n_sync_false++;
+    rx_trace(tr, ORC_TR_NOTSYNCED, entry_pos, cause, io->n_sync_false, 0, 0);
     while (currentStrength / 50 > 0.50 * R.sLevel) {
         orc_cf32 s = rx_get_sample(&R, R.coarse + R.fine); if (R.failed) goto done;
         envBuffer[syncBufferIndex] = l1_norm(s);
         currentStrength += envBuffer[syncBufferIndex] - envBuffer[(syncBufferIndex - 50) & 32767];
         syncBufferIndex = (syncBufferIndex + 1) & 32767;
         counter++;
-        if (counter > ORC_TF) goto notSynced;
+        if (counter > ORC_TF) { cause = ORC_CAUSE_HOPELESS_FALL; goto notSynced; }
     }
+    rx_trace(tr, ORC_TR_FALL, counter, R.pos, 0, 0, 0);
     counter = 0;
     while (currentStrength / 50 < 0.75 * R.sLevel) {
         orc_cf32 s = rx_get_sample(&R, R.coarse + R.fine); if (R.failed) goto done;
@@ -1066,8 +1083,9 @@ notSynced:
         currentStrength += envBuffer[syncBufferIndex] - envBuffer[(syncBufferIndex - 50) & 32767];
         syncBufferIndex = (syncBufferIndex + 1) & 32767;
         counter++;
-        if (counter > ORC_TNULL + 50) goto notSynced;
+        if (counter > ORC_TNULL + 50) { cause = ORC_CAUSE_HOPELESS_RISE; goto notSynced; }
     }
+    rx_trace(tr, ORC_TR_RISE, counter, R.pos, 0, 0, 0);
 SyncOnPhase:
     {
         int64_t buf_pos = R.pos;
@@ -1076,7 +1094,8 @@ SyncOnPhase:
         io->n_cir++;
         startIndex = orc_find_index(ofdmBuffer, io->fft_placement, ir);
         if (frame < io->sidx_cap && io->start_index) { io->start_index[frame] = startIndex; io->frame_pos[frame] = buf_pos; }
-        if (startIndex < 0) goto notSynced;
+        int64_t* attempt = rx_trace(tr, ORC_TR_ATTEMPT, buf_pos, startIndex, R.coarse, R.fine, io->n_sync_false);
+        if (startIndex < 0) { cause = ORC_CAUSE_WINDOW_FAILED; goto notSynced; }
         memmove(ofdmBuffer, &ofdmBuffer[startIndex], sizeof(orc_cf32) * (size_t)(ORC_TU - startIndex));
         int ofdmBufferIndex = ORC_TU - startIndex;
         io->n_sync_true++;
@@ -1145,6 +1164,7 @@ SyncOnPhase:
             }
         }
         if (frame < io->corr_cap && io->corr) { io->corr[2 * frame] = R.fine; io->corr[2 * frame + 1] = R.coarse; }
+        if (attempt) { attempt[5] = 1; attempt[6] = R.fine; attempt[7] = R.coarse; }
         if (R.fine > 1000 / 2) { R.coarse += 1000; R.fine -= 1000; }
         else if (R.fine < -1000 / 2) { R.coarse -= 1000; R.fine += 1000; }
         frame++;
@@ -1155,4 +1175,18 @@ done:
     for (int i = 0; i < io->n_subch; i++) orc_subch_free(&subs[i]);
     free(subs); free(dem); free(ofdmBuffer); free(syms); free(cif);
     return 0;
+}
+
+int orc_receiver_run(orc_run_io* io)
+{
+    rx_trace_t tr = {NULL, NULL, 0, 0};
+    return receiver_run(io, &tr);
+}
+
+int orc_receiver_run_traced(orc_run_io* io, int32_t* trace_kind, int64_t* trace_val, int trace_cap, int* n_trace)
+{
+    rx_trace_t tr = {trace_kind, trace_val, trace_cap, 0};
+    const int r = receiver_run(io, &tr);
+    if (n_trace) *n_trace = tr.n;
+    return r;
 }

@@ -157,6 +157,21 @@ typedef struct {
     void* tii_state; const int32_t* tii_rank; orc_tii_event* tii_ev; int tii_cap; int n_tii;
 } orc_run_io;
 int orc_receiver_run(orc_run_io* io);
+/* the same run with a trace of the acquisition head (ofdm-processor.cpp:256-350), events in stream order: trace_kind[i] = ORC_TR_*,
+ * trace_val[ORC_TR_VALS * i ..] = the event's values (below), trace_cap entries (NULL / 0 = none kept); *n_trace counts every event,
+ * kept or not.  (A call of its own: orc_run_io keeps the layout its callers were written for.) */
+int orc_receiver_run_traced(orc_run_io* io, int32_t* trace_kind, int64_t* trace_val, int trace_cap, int* n_trace);
+#define ORC_TR_VALS 8
+#define ORC_TR_NOTSYNCED 1    /* the search starts (again): position of the first of its 50 samples, cause (ORC_CAUSE_*), n_sync_false after it */
+#define ORC_TR_FALL 2         /* the first threshold loop (:285) ends: its counter, position */
+#define ORC_TR_RISE 3         /* the second one (:306) ends: its counter, position */
+#define ORC_TR_ATTEMPT 4      /* SyncOnPhase (:337-350): buf_pos, start_index, coarse, fine at that moment, n_sync_false at that moment;
+                               * then 1, fine, coarse as corr[] has them once the frame is through (else 0, 0, 0).  The k-th attempt's
+                               * impulse response is cir[k] */
+#define ORC_CAUSE_PRIMED 0
+#define ORC_CAUSE_HOPELESS_FALL 1
+#define ORC_CAUSE_HOPELESS_RISE 2
+#define ORC_CAUSE_WINDOW_FAILED 3
 
 #ifdef __cplusplus
 }

@@ -64,6 +64,7 @@ struct Rec : RadioControllerInterface {
 
 struct MemInput : InputInterface {
     const DSPCOMPLEX* data; int64_t n; int64_t pos = 0;
+    std::atomic<bool> armed{true};       // false: nothing to read yet (the receiver waits, is_ok() stays true)
     MemInput(const float* iq, int64_t n_) : data((const DSPCOMPLEX*)iq), n(n_) {}
     void setFrequency(int) override {}
     int getFrequency() const override { return 0; }
@@ -73,7 +74,7 @@ struct MemInput : InputInterface {
     void reset() override {}
     int32_t getSamples(DSPCOMPLEX* b, int32_t size) override { int64_t k = size; if (k > n - pos) k = n - pos; memcpy(b, data + pos, k * sizeof(DSPCOMPLEX)); pos += k; return (int32_t)k; }
     std::vector<DSPCOMPLEX> getSpectrumSamples(int) override { return {}; }
-    int32_t getSamplesToRead() override { int64_t k = n - pos; return (int32_t)(k > (1 << 20) ? (1 << 20) : k); }
+    int32_t getSamplesToRead() override { if (!armed) return 0; int64_t k = n - pos; return (int32_t)(k > (1 << 20) ? (1 << 20) : k); }
     float setGain(int) override { return 0; }
     float getGain() const override { return 0; }
     int getGainCount() override { return 0; }
@@ -111,6 +112,10 @@ int gpu_receiver_run(gpu_run_io* io)
     std::vector<NullProgrammeHandler> handlers(io->n_subch > 0 ? io->n_subch : 1);
     try {
         GpuRadioReceiver rx(rec, in, rro);
+        // the worker applies pending sub-channels at the top of every pass and decodes the first frames in its first pass with samples:
+        // it gets none until every sub-channel is registered (ref_harness.cpp arms its input the same way), or the first frame's
+        // logical frames are missing from the dump whenever the worker's first pass wins the race
+        in.armed = false;
         rx.restart(false);
         for (int i = 0; i < io->n_subch; i++) {
             const gpu_subch& s = io->subch[i];
@@ -121,6 +126,7 @@ int gpu_receiver_run(gpu_run_io* io)
             sub.protectionSettings.eepLevel = (EEPProtectionLevel)s.eepLevel;
             rx.addSubchannel(handlers[i], s.dabplus ? AudioServiceComponentType::DABPlus : AudioServiceComponentType::DAB, std::string(s.dump_path), sub);
         }
+        in.armed = true;
         while (!rec.failed) std::this_thread::sleep_for(std::chrono::milliseconds(2));
         rx.stop();
     } catch (const std::exception& e) {

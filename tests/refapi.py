@@ -103,6 +103,31 @@ def receiver_run(iq, subchs=(), dump_dir="/tmp", disable_coarse=False, fft_place
                 rs_calls=list(io.rs_calls), rs_uncorr=list(io.rs_uncorr), rs_corr=list(io.rs_corr))
 
 
+REF_ACQUIRE_SO = os.path.join(ROOT, "oracle", "_ref", "libwelle_ref_acquire.so")
+_ref_acquire = None
+
+
+def have_ref_acquire():
+    return os.path.exists(REF_ACQUIRE_SO)
+
+
+def ref_acquire_run(iq, cap):
+    """the real reference RadioReceiver over a cf32 stream, listening to its window searches (oracle/ref_acquire_harness.cpp: a library
+    of its own beside the harness library) -> attempts = [(stream position of the search's first sample, found)] of every SyncOnPhase
+    attempt, their impulse responses, and the onSyncChange(true) / (false) counts.  cap: attempts that can be kept"""
+    global _ref_acquire
+    if _ref_acquire is None:
+        _ref_acquire = C.CDLL(REF_ACQUIRE_SO)
+        _ref_acquire.ref_acquire_run.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    iq = np.ascontiguousarray(iq, np.complex64)
+    pos = np.zeros(cap, np.int64); before = np.zeros(cap, np.int32); cir = np.zeros((cap, 2048), np.float32); counts = np.zeros(3, np.int32)
+    assert _ref_acquire.ref_acquire_run(_p(iq), len(iq), _p(pos), _p(before), _p(cir), cap, _p(counts)) == 0
+    n = int(counts[0]); assert n <= cap, (n, cap)
+    after = list(before[1:n]) + [counts[1]]                     # onSyncChange(true) calls seen by the NEXT attempt (by the end of the run)
+    return dict(attempts=[(int(pos[k]), bool(after[k] > before[k])) for k in range(n)], cir=cir[:n],
+                n_sync_true=int(counts[1]), n_sync_false=int(counts[2]))
+
+
 def ref_rawfile_read(path, fmt, n_samples):
     """the reference's CRAWFile (input/raw_file.cpp) reading `path` as `fmt`: the first n_samples it hands to getSamples()"""
     out = np.zeros(n_samples, np.complex64)
@@ -245,6 +270,9 @@ class OrcRunIO(C.Structure):
                 ("n_fib", C.c_int), ("n_frames", C.c_int), ("n_snr", C.c_int), ("n_sync_true", C.c_int), ("n_sync_false", C.c_int), ("n_cir", C.c_int),
                 ("freqsync_sel", C.c_int),
                 ("tii_state", C.c_void_p), ("tii_rank", C.c_void_p), ("tii_ev", C.c_void_p), ("tii_cap", C.c_int), ("n_tii", C.c_int)]
+
+TR_VALS, TR_NOTSYNCED, TR_FALL, TR_RISE, TR_ATTEMPT = 8, 1, 2, 3, 4           # ORC_TR_* of oracle/dabphy_oracle.h
+CAUSE_PRIMED, CAUSE_HOPELESS_FALL, CAUSE_HOPELESS_RISE, CAUSE_WINDOW_FAILED = 0, 1, 2, 3
 
 
 TII_EVENT_DTYPE = np.dtype([("frame", "<i4"), ("comb", "<i4"), ("pattern", "<i4"), ("delay_samples", "<i4"), ("error", "<f4")])
@@ -451,7 +479,9 @@ def ref_tii_run(nulls, prss):
     return _tii_sorted(ev[:n])
 
 
-def orc_receiver_run(iq, subchs=(), disable_coarse=False, fft_placement=2, want_soft=False, freqsync=2, tii=False):
+def orc_receiver_run(iq, subchs=(), disable_coarse=False, fft_placement=2, want_soft=False, freqsync=2, tii=False, cir_cap=None, trace_cap=0):
+    """cir_cap: impulse responses kept (one per window search, found or not; default: frames + 2).  trace_cap > 0 adds "trace": the
+    acquisition head's events in stream order as (kind, [TR_VALS values]) (ORC_TR_* of oracle/dabphy_oracle.h)"""
     iq = np.ascontiguousarray(iq, np.complex64); nf = len(iq) // 196608 + 2
     io = OrcRunIO(); io.iq = _p(iq); io.n_samples = len(iq)
     io.disable_coarse = int(disable_coarse); io.fft_placement = fft_placement
@@ -464,11 +494,13 @@ def orc_receiver_run(iq, subchs=(), disable_coarse=False, fft_placement=2, want_
         b = np.zeros(nf * 4 * s.frame_bytes, np.uint8); bufs.append(b); ptrs[i] = b.ctypes.data; caps[i] = len(b)
     io.n_subch = len(subchs); io.subch = cfg; io.msc = ptrs; io.msc_cap = caps; io.msc_len = lens
     fib = np.zeros((nf * 12, 33), np.uint8); io.fib = _p(fib); io.fib_cap = nf * 12
-    cir = np.zeros((nf, 2048), np.float32); io.cir = _p(cir); io.cir_cap = nf
+    ncir = nf if cir_cap is None else cir_cap
+    cir = np.zeros((ncir, 2048), np.float32); io.cir = _p(cir); io.cir_cap = ncir
     con = np.zeros((nf, 1200), np.complex64); io.con = _p(con); io.con_cap = nf
     nul = np.zeros((nf, 2656), np.complex64); io.nul = _p(nul); io.nul_cap = nf
     snr = np.zeros(nf, np.float32); io.snr = _p(snr); io.snr_cap = nf
     corr = np.zeros((nf, 2), np.int32); io.corr = _p(corr); io.corr_cap = nf
+    tk = np.zeros(max(1, trace_cap), np.int32); tv = np.zeros((max(1, trace_cap), TR_VALS), np.int64)
     sidx = np.zeros(nf, np.int32); fpos = np.zeros(nf, np.int64); io.start_index = _p(sidx); io.frame_pos = _p(fpos); io.sidx_cap = nf
     soft = np.zeros((nf if want_soft else 0, 75, 3072), np.int8)
     io.soft = _p(soft) if want_soft else None; io.soft_cap = nf if want_soft else 0
@@ -476,14 +508,22 @@ def orc_receiver_run(iq, subchs=(), disable_coarse=False, fft_placement=2, want_
         orc().orc_tii_state_bytes.restype = C.c_size_t
         tst = np.zeros(orc().orc_tii_state_bytes(), np.uint8); trank = orc_tii_rank(); tev = np.zeros(16 * nf, TII_EVENT_DTYPE)
         io.tii_state = _p(tst); io.tii_rank = _p(trank); io.tii_ev = _p(tev); io.tii_cap = len(tev)
-    orc().orc_receiver_run(C.byref(io))
+    n_trace = C.c_int(0)
+    if trace_cap:
+        orc().orc_receiver_run_traced(C.byref(io), _p(tk), _p(tv), trace_cap, C.byref(n_trace))
+    else:
+        orc().orc_receiver_run(C.byref(io))
     k = io.n_frames
     if tii:
         return dict(nul=nul[:k], tii=_tii_sorted(tev[:io.n_tii]), n_frames=k, fib=fib[:io.n_fib], corr=corr[:k])
-    return dict(fib=fib[:io.n_fib], cir=cir[:min(io.n_cir, nf)], con=con[:k], nul=nul[:k], snr=snr[:io.n_snr], corr=corr[:k],
+    extra = {}
+    if trace_cap:
+        assert n_trace.value <= trace_cap, (n_trace.value, trace_cap)
+        extra["trace"] = [(int(tk[i]), [int(v) for v in tv[i]]) for i in range(n_trace.value)]
+    return dict(fib=fib[:io.n_fib], cir=cir[:min(io.n_cir, ncir)], con=con[:k], nul=nul[:k], snr=snr[:io.n_snr], corr=corr[:k],
                 start_index=sidx[:k], frame_pos=fpos[:k], soft=soft[:k] if want_soft else None,
                 msc=[bufs[i][:lens[i]].tobytes() for i in range(len(subchs))],
-                n_sync_true=io.n_sync_true, n_sync_false=io.n_sync_false, n_frames=k)
+                n_sync_true=io.n_sync_true, n_sync_false=io.n_sync_false, n_frames=k, n_cir=io.n_cir, **extra)
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import acquire_cases as A
 import parity_cases as P
 import refapi as R
 import sf_cases as S
@@ -386,3 +387,19 @@ def test_process_prs_on_the_directed_coarse_cases(oracle_built, freqsync):
         for c, (s, _, _) in zip(SC.RECEIVER_CASES, SC.ORACLE_RECEIVER[m][freqsync]):
             ri, _ = R.ref_find_index(c.iq[:2048], m)
             assert ri == s and R.ref_coarse_prs(c.iq[s:s + 2048], freqsync) == R.orc_coarse_prs_method(c.iq[s:s + 2048], freqsync), (c.name, m, freqsync)
+
+
+@pytest.mark.skipif(not R.have_ref_acquire(), reason="oracle/_ref/libwelle_ref_acquire.so not built (needs /root/reference)")
+@pytest.mark.parametrize("name", A.FAMILIES)
+def test_acquisition_attempts_on_the_directed_streams(oracle_built, name):
+    """OFDMProcessor::run itself over every stream of tests/acquire_cases.py -- the inputs the acquisition head of k_sync.hip is checked on
+    (tests/test_emu_acquire.py, tests/test_gpu_acquire.py): where each window search starts in the stream (the input's read position inside
+    onNewImpulseResponse, which fires on the pulling thread right behind the search's one getSamples(T_u)), whether it found a window, every
+    impulse response, and the final onSyncChange counts equal the restatement's trace.  Without this the device would be pinned to our own
+    restatement of the null-symbol search alone.  (A NaN equals a NaN: acquire_cases.same_bits.)"""
+    for c in A.family(name):
+        o = A.oracle(name)[c.name]
+        r = R.ref_acquire_run(c.iq, len(o.attempts) + 16)
+        assert r["attempts"] == [(a.pos, a.start_index >= 0) for a in o.attempts], c.name
+        assert (r["n_sync_false"], r["n_sync_true"]) == (o.n_sync_false, o.n_sync_true), (c.name, r["n_sync_false"], r["n_sync_true"], o.n_sync_false, o.n_sync_true)
+        assert len(r["cir"]) == len(o.cir) and all(A.same_bits(x, y) for x, y in zip(r["cir"], o.cir)), c.name

@@ -348,6 +348,10 @@ __global__ void __launch_bounds__(FINISH_THREADS, SYNC_FINISH_WIDE_OCC) k_sync_f
 __device__ __forceinline__ double slevel_in(float a) { return 0.00001 * (double)a; }
 __device__ __forceinline__ float slevel_step(double in, float level) { return (float)(in + (1 - 0.00001) * (double)level); }
 
+// the two ends of sLevel's bracket have met: equal -- or both NaN, which the level stays, whatever it started from, once a sample that is
+// not a number has gone through the recurrence (the reference's level is NaN then too; NaN == NaN is false)
+__device__ __forceinline__ bool slevel_met(float lo, float hi) { return lo == hi || (lo != lo && hi != hi); }
+
 // ---- sLevel catches up with the samples that were pulled while tracking (ofdm-processor.cpp:216: once per sample, float result
 // of a double expression).  Exact when the history reaches back to the last point at which the level was exact; otherwise two
 // runs from the extremes of what the level can be bracket it (the update is monotone in the level): if they have met by the end,
@@ -384,7 +388,7 @@ __device__ __forceinline__ void slevel_replay(const SyncArgs& A, const int b, Rx
                 __syncthreads();
                 if (t == 0) {
                     float lo = s_lo, hi = s_hi;
-                    const bool one = lo == hi;                                   // exact start: a single chain
+                    const bool one = slevel_met(lo, hi);                         // exact start: a single chain
                     int i = 0;
                     for (; i + 16 <= m; i += 16) {                               // operands fetched 16 at a time, off the dependent chain
                         const float4 q0 = *reinterpret_cast<const float4*>(l1 + i), q1 = *reinterpret_cast<const float4*>(l1 + i + 4),
@@ -412,7 +416,7 @@ __device__ __forceinline__ void slevel_replay(const SyncArgs& A, const int b, Rx
         }
     }
     if (t == 0) {
-        if (s_lo != s_hi) s_st.n_relock_inexact += 1;
+        if (!slevel_met(s_lo, s_hi)) s_st.n_relock_inexact += 1;
         s_st.s_level = s_hi;
         s_st.hist_count = 0; s_st.hist_head = 0; s_st.hist_dropped = 0;
     }
