@@ -686,13 +686,11 @@ int dabphy_time_fused_msc(dabphy_handle* h, uint32_t iters, float* ms)
     HIPCHK(h, hipDeviceSynchronize());                       // alone on the device: nothing of the pipeline beside it
     ScopedEvent e0, e1;
     HIPCHK(h, e0.create()); HIPCHK(h, e1.create());
-    const FusedSplit sp{h->tb_no_walkers ? nullptr : h->tb_stream, h->ev_tb_fork, h->ev_tb_join};
-    auto again = [&]() { if (P.use_sp) launch_sp(P.args, P.sp_two, P.sp_variant, h->stream); else launch_viterbi_fused(P.args, P.variant, P.n_slots, h->stream, P.args.done ? &sp : nullptr); };
-    again();                                                                  // (same inputs, same outputs: the launch is idempotent)
+    launch_plan(h, h->stream);                                                // (same inputs, same outputs: the launch is idempotent)
     HIPCHK(h, hipEventRecord(e0, h->stream));
     // (split traceback: the launch forks a second stream off and joins it through two events the NEXT launch records again -- the stream
     // is drained between launches so that no wait is pending on an event when it is re-recorded; ~20 us per launch in the figure)
-    for (uint32_t i = 0; i < iters; i++) { again(); if (P.args.done) HIPCHK(h, hipStreamSynchronize(h->stream)); }
+    for (uint32_t i = 0; i < iters; i++) { launch_plan(h, h->stream); if (P.args.done) HIPCHK(h, hipStreamSynchronize(h->stream)); }
     HIPCHK(h, hipEventRecord(e1, h->stream));
     HIPCHK(h, hipEventSynchronize(e1));
     float t = 0; HIPCHK(h, hipEventElapsedTime(&t, e0, e1));

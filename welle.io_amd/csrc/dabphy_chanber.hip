@@ -23,22 +23,7 @@ uint32_t longest_list(const dabphy_handle* h)
     return (uint32_t)n;
 }
 
-void add_groups(std::vector<uint32_t>& work, uint32_t ci, int64_t n_cw)
-{
-    for (int64_t g = 0; g < (n_cw + 63) / 64; g++) work.push_back((ci << 24) | (uint32_t)g);
-}
-
-// a table of the pass in its own buffer: uploaded when its contents or its buffer changed
-template <typename T> int upload_if_changed(dabphy_handle* h, DevBuf& b, std::vector<T>& have, const std::vector<T>& want)
-{
-    const void* const before = b.p;
-    if (int r = ensure(h, b, std::max<size_t>(want.size(), 1) * sizeof(T))) return r;
-    if (b.p == before && have.size() == want.size() && (want.empty() || !memcmp(have.data(), want.data(), want.size() * sizeof(T)))) return 0;
-    HIPCHK(h, hipStreamSynchronize(h->stream));        // (an earlier upload may still be reading `have`: a pageable source is not always staged before the call returns)
-    have = want;                                       // the handle's own storage outlives the copy
-    if (!want.empty()) HIPCHK(h, hipMemcpyAsync(b.p, have.data(), want.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
-    return 0;
-}
+void add_groups(std::vector<uint32_t>& work, uint32_t ci, int64_t n_cw) { for (int64_t g = 0; g < (n_cw + 63) / 64; g++) work.push_back(work_item(ci, (uint32_t)g)); }
 }
 
 extern "C" {
@@ -48,15 +33,13 @@ int chanber_reserve(dabphy_handle* h, uint32_t F)
     ChanBer& c = h->ber;
     if (!c.on) return DABPHY_OK;
     const uint32_t B = h->cfg.n_ensembles, R = 4 * F;
-    if (h->classes.size() + 1 > 255) { h->err = "more than 254 protection classes with the channel BER pass"; return DABPHY_ERR_INVALID; }
+    if (h->classes.size() + 1 > WORK_MAX_CLASSES) { h->err = "more than 254 protection classes with the channel BER pass"; return DABPHY_ERR_INVALID; }
     std::vector<FusedClass> cls; std::vector<uint32_t> work, first, slots;
     uint64_t at = 0;
     cls.push_back(fic_fused_class(h, h->s_fib.as<uint8_t>(), (int)(B * R), -1));
     first.push_back(0); add_groups(work, 0, (int64_t)B * R); at += (uint64_t)B * R;
     for (const auto& mc : h->classes) {
-        FusedClass fc{};
-        fc.pairs = mc.pair_tab.as<MscPair>(); fc.map = mc.map.as<map_t>(); fc.out = mc.out.as<uint8_t>();
-        fc.nbits = mc.prot.nbits; fc.nsteps = fc.nbits + 6; fc.n_pairs = (int32_t)mc.pairs.size(); fc.n_cw = (int32_t)(R * mc.pairs.size()); fc.kind = 0; fc.dedisperse = 1;
+        const FusedClass fc = msc_fused_class(mc, F, -1);                 // (the pass gathers by the map: no step table)
         first.push_back((uint32_t)at); add_groups(work, (uint32_t)cls.size(), fc.n_cw); at += (uint64_t)fc.n_cw;
         cls.push_back(fc);
     }
@@ -181,7 +164,7 @@ int dabphy_channel_ber(dabphy_handle* h, const dabphy_protection* prot, const in
     DeviceBind dev_(h);
     if (!h || !prot || !in || !decoded || !out || n_codewords == 0 || !protection_valid(prot) || prot->nbits > PRBS_MAX_BITS) return DABPHY_ERR_INVALID;
     const uint32_t n_groups = (n_codewords + 63) / 64;
-    if (n_groups > 0xffffffu) { h->err = "dabphy_channel_ber: too many code words"; return DABPHY_ERR_INVALID; }
+    if (n_groups > WORK_MAX_GROUPS) { h->err = "dabphy_channel_ber: too many code words"; return DABPHY_ERR_INVALID; }
     const std::vector<map_t> m = depuncture_map(prot);
     const size_t n_in = (size_t)protection_input_bits(prot), nbytes = (size_t)prot->nbits / 8;
     // the table: the class, the first record of class 0, the work list
@@ -193,7 +176,7 @@ int dabphy_channel_ber(dabphy_handle* h, const dabphy_protection* prot, const in
     fc.map = h->map.as<map_t>(); fc.out = h->vout.as<uint8_t>(); fc.nbits = prot->nbits; fc.nsteps = prot->nbits + 6; fc.n_cw = (int32_t)n_codewords; fc.n_pairs = 1;
     fc.kind = 2; fc.dedisperse = 1;
     memcpy(tab.data(), &fc, sizeof fc);
-    for (uint32_t g = 0; g < n_groups; g++) tab[sizeof(FusedClass) / 4 + 4 + g] = g;
+    for (uint32_t g = 0; g < n_groups; g++) tab[sizeof(FusedClass) / 4 + 4 + g] = work_item(0, g);
     HIPCHK(h, hipMemcpyAsync(h->map.p, m.data(), m.size() * sizeof(map_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->in8.p, in, n_in * n_codewords, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->vout.p, decoded, nbytes * n_codewords, hipMemcpyHostToDevice, h->stream));

@@ -3,7 +3,8 @@
 //   dabphy_api.hip          create / destroy / options / sub-channel classes, the stateless seams (demod, Viterbi, FIC, RS) and the timing drivers
 //   dabphy_stream.hip       sample rings (bind / upload / write / raw formats), the wideband front end's open and write calls (dabphy_handle::Wideband), the synchroniser's chain and wide pass, reset
 //   dabphy_process.hip      dabphy_process: the pipelined schedules, exact batch mode (replay), the decode of one batch as named steps
-//   dabphy_fused.hip        the fused decode's host side: per-class step tables, the launch plan (build, classes, work list)
+//   dabphy_fused.hip        the fused decode's host side: per-class step tables; the launch plan as named steps (fused_plan: choose_shape, admit_classes,
+//                           build_work_list, lay_out_scratch, reserve_buffers, upload_changed, keep_plan), launch_plan, the one-class state-parallel launches
 //   dabphy_superframes.hip  Reed-Solomon seams and the DAB+ superframe filter
 //   dabphy_mp2.hip          classic DAB (MP2) services: audio kinds, the MP2 frame check and its unit entry
 //   dabphy_getters.hip      everything a caller reads back after a batch, profiling, TII
@@ -13,6 +14,7 @@
 //                           impulse response, the three window-index methods), sync_fine.h (the fine corrector's step and its interval test; host-compilable); block_reduce.h (their work-group reduction)
 //   k_wideband.hip, k_resample.hip   the wideband front end's main kernels (integer, rational rate); capture_sample (dabphy_kernels.h) and k_capture_carry (k_ingest.hip) serve both
 //   soft_layout.h           where a code word's soft bits lie in the soft-bit ring, for kernels and host alike (dabphy_fused.hip's step tables)
+//   decode_work.h           the decoders' work-item word and the state-parallel kernels' history geometry, for kernels and host alike (through dabphy_kernels.h)
 // Ownership: a device buffer (DevBuf) owns itself and is freed by its destructor; streams, events and page-locked blocks are created
 // through new_stream / new_event / pinned_alloc below and nowhere else, which register them with the handle for dabphy_destroy.
 #pragma once
@@ -164,7 +166,7 @@ struct dabphy_handle {
     // work list; rebuilt when the batch depth, the class set or a buffer address changes (dabphy_fused.hip)
     struct FusedPlan {
         bool valid = false; uint32_t F = 0; bool want_fic = false; bool fic_in = false;
-        int variant = 0, n_slots = 0; size_t dec_slot_cells = 0;
+        int variant = 0, n_slots = 0;
         bool use_sp = false; int sp_variant = 0; bool sp_two = false;   // ... two code words per wavefront (k_viterbi_sp2)         // the batch is small: one wavefront per code word (k_viterbi_sp) instead of 64 code words per wavefront
         std::vector<int> class_idx;                      // classes decoded by the fused launch (the others take k_msc_gather + k_viterbi)
         std::vector<FusedClass> host_cls; std::vector<uint32_t> host_work, host_dec_off;
@@ -345,6 +347,29 @@ template <typename T> int upload_table(dabphy_handle* h, DevBuf& b, const std::v
     HIPCHK(h, hipMemcpyAsync(b.p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
     return 0;
 }
+// ... or one the handle keeps a copy of (`have`), uploaded only when its contents or its buffer changed, and never replaced under an
+// earlier copy that may still read it (a pageable source is not always staged before the call returns).  table_holds: the contents
+// are the same; upload_kept: `have` becomes `want` and goes up -- the caller has waited for the stream if `have` was ever uploaded;
+// the handle's own storage outlives the copy, which the stream orders before the launches that read the table
+template <typename T> bool table_holds(const std::vector<T>& have, const std::vector<T>& want)
+{
+    return have.size() == want.size() && (want.empty() || !memcmp(have.data(), want.data(), want.size() * sizeof(T)));
+}
+template <typename T> int upload_kept(dabphy_handle* h, DevBuf& b, std::vector<T>& have, const std::vector<T>& want)
+{
+    have = want;
+    if (!want.empty()) HIPCHK(h, hipMemcpyAsync(b.p, have.data(), want.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+// ... a table in a buffer of its own (the channel BER pass; the launch plan's tables move with buf_gen and share one wait: dabphy_fused.hip)
+template <typename T> int upload_if_changed(dabphy_handle* h, DevBuf& b, std::vector<T>& have, const std::vector<T>& want)
+{
+    const void* const before = b.p;
+    if (int r = ensure(h, b, std::max<size_t>(want.size(), 1) * sizeof(T))) return r;
+    if (b.p == before && table_holds(have, want)) return 0;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return upload_kept(h, b, have, want);
+}
 
 // Streams (non-blocking; high_priority: the device's greatest), events (without timing unless asked) and page-locked host blocks of a
 // handle: created here, registered for dabphy_destroy.  *out stays null on failure.
@@ -469,6 +494,14 @@ inline FusedClass fic_fused_class(const dabphy_handle* h, uint8_t* out, int n_cw
     if (variant >= 0) { fc.steps = h->fic_steps[variant].as<MscStep>(); fc.n_windows = h->fic_windows[variant]; }
     return fc;
 }
+// ... and an MSC protection class at F frames per call: every pair's 4 F code words, written to the class's output
+inline FusedClass msc_fused_class(const dabphy_handle::MscClass& c, uint32_t F, int variant)
+{
+    FusedClass fc{}; fc.pairs = c.pair_tab.as<MscPair>(); fc.map = c.map.as<map_t>(); fc.out = c.out.as<uint8_t>(); fc.nbits = c.prot.nbits; fc.nsteps = fc.nbits + 6;
+    fc.n_pairs = (int32_t)c.pairs.size(); fc.n_cw = (int32_t)(4 * F * (uint32_t)c.pairs.size()); fc.kind = 0; fc.dedisperse = 1;
+    if (variant >= 0) { fc.steps = c.steps[variant].as<MscStep>(); fc.n_windows = c.n_windows[variant]; }
+    return fc;
+}
 // the FIC of ONE class, state-parallel or through k_fic_gather + k_viterbi (dabphy_fused.hip: fic_one_prepare / fic_one_launch): what
 // sp_single_ok decided, and the prepared arguments of either path
 struct FicOneClass { bool sp = false; FusedArgs spa{}; FicGatherArgs g{}; VitArgs v{}; };
@@ -492,6 +525,7 @@ DABPHY_INTERNAL size_t mp2_stride();
 DABPHY_INTERNAL int upload_pairs(dabphy_handle* h, dabphy_handle::MscClass& cls);
 DABPHY_INTERNAL int fused_class_tables(dabphy_handle* h, const dabphy_protection& prot, bool fic, DevBuf (&steps)[FUSED_VARIANTS], int (&n_windows)[FUSED_VARIANTS]);   // dabphy_fused.hip
 DABPHY_INTERNAL int fused_plan(dabphy_handle* h, uint32_t F, bool want_fic);
+DABPHY_INTERNAL void launch_plan(const dabphy_handle* h, hipStream_t s);                                         // the plan as queued: dabphy_process's launch, dabphy_time_fused_msc
 DABPHY_INTERNAL bool sp_single_ok(const dabphy_handle* h, uint64_t n_cw, int nsteps);
 DABPHY_INTERNAL int sp_single_reserve(dabphy_handle* h, uint64_t n_cw, int nsteps);
 DABPHY_INTERNAL int sp_single_prepare(dabphy_handle* h, const FusedClass& fc, FusedArgs& a, hipStream_t st);

@@ -1,6 +1,7 @@
 // welle.io_amd/csrc/dabphy_kernels.h -- device-side data structures and kernel argument blocks.
 #pragma once
 #include "dabphy_common.h"
+#include "decode_work.h"
 
 namespace dabphy {
 
@@ -197,7 +198,7 @@ struct FusedArgs {
     const int8_t* soft; size_t ens_stride; int soft_ring; int n_ens, n_frames;
     const FrameDesc* desc;
     const FusedClass* cls;
-    const uint32_t* work; uint32_t n_work;     // work list: class << 24 | group of 64 code words, longest code words first
+    const uint32_t* work; uint32_t n_work;     // work list of work_item()s (decode_work.h), longest code words first
     uint32_t* next;                            // its dynamic cursor (zeroed by the launcher)
     uint2* dec; size_t dec_slot_cells;         // decision scratch of work-group i: dec + i * dec_slot_cells ([step][64 lanes] cells)
     const uint32_t* dec_off;                   // k_viterbi_fused: nullptr, or the scratch goes by work ITEM: item i at dec + dec_off[i] * 64 cells
@@ -209,7 +210,7 @@ struct FusedArgs {
     int fic_frame_sel;                         // kind 1: 0 = every frame of the batch; f + 1 = frame f only (n_cw = 4 B)
     size_t fic_frame_stride;                   // kind 1: bytes between frame slots of `soft` (0: SOFT_PER_FRAME, the ring)
     const int8_t* lin_in; size_t lin_stride;   // kind 2
-    int sp2_warm;                              // k_traceback_sp2: history blocks (30 steps each) a stretch's walk runs in over before its own blocks
+    int sp2_warm;                              // k_traceback_sp2: history blocks (HIST_STEPS steps each) a stretch's walk runs in over before its own blocks
     int sp2_resident;                          // k_traceback_sp2: groups of 64 code words up to which a launch cuts the code word into four stretches (above: three)
 };
 // variant = index into FUSED_ROWS; n_slots = work-groups (one wave each) to launch
@@ -219,19 +220,19 @@ void launch_viterbi_fused(const FusedArgs& a, int variant, int n_slots, hipStrea
 int fused_wave_slots(int variant);             // resident waves of that variant on the current device
 // State-parallel decode of the same work (k_viterbi_sp.hip): one wavefront per CODE WORD, lanes = the 64 trellis states -- the shape for
 // batches too small to fill the device with 64-code-word waves.  lds_variant = index into SP_MAXSTEPS (the longest code word of the launch);
-// one work-group per code word slot: a.n_work * 64 of them; a.dec holds a.dec_slot_cells decision words per work-group.
+// one work-group per code word slot: a.n_work * 64 of them; a.dec holds a.dec_slot_cells = hist_cells(steps, false) cells per work-group.
 constexpr int SP_VARIANTS = 3;
 constexpr int SP_MAXSTEPS[SP_VARIANTS] = {1542, 3078, 9222};     // <= 64, <= 128, <= 384 kbit/s (24 * bitrate + 6 trellis steps)
 void launch_viterbi_sp(const FusedArgs& a, int lds_variant, hipStream_t s);
 void launch_selftest_pair_exchange(unsigned* out, hipStream_t s);
 // ... two code words per wavefront (k_viterbi_sp2.hip): half the instructions per code word; one work-group per PAIR of code word slots:
-// a.n_work * 32 of them, a.dec_slot_cells = (steps / 30 + 1) * 64 per work-group.  Its LDS table holds four 16-bit sums per trellis
+// a.n_work * 32 of them, a.dec_slot_cells = hist_cells(steps, true) per work-group (decode_work.h).  Its LDS table holds four 16-bit sums per trellis
 // step and code word for 480 steps at a time: code words of any length pass through it chunk by chunk (lds_variant is ignored)
 constexpr int SP2_VARIANTS = 2;
 void launch_viterbi_sp2(const FusedArgs& a, int lds_variant, hipStream_t s);
 void launch_selftest_half_exchange(unsigned* out, hipStream_t s);
 
-// Channel BER pass (k_chanber.hip): one wavefront per code word of f.work's groups (class << 24 | group of 64, as the decoders list
+// Channel BER pass (k_chanber.hip): one wavefront per code word of f.work's groups (work_item()s, as the decoders list
 // them); f names what locate() reads -- the soft-bit ring and the descriptors, or a seam's plain array --, the classes (map, pairs, out,
 // nbits, dedisperse) and the PRBS words.  Code word cw of class c -> out[first[c] + cw] = (errors, compared)
 struct BerArgs { FusedArgs f; const uint32_t* first; uint2* out; };

@@ -247,8 +247,7 @@ static int launch_fused(dabphy_handle* h, const Batch& b)
     FusedArgs fa = h->fplan.args; fa.desc = b.d_desc;
     h->fplan.args = fa; h->fplan.launched = true;
     mark(h, dabphy_handle::ST_MSC_VITERBI, false);
-    if (h->fplan.use_sp) launch_sp(fa, h->fplan.sp_two, h->fplan.sp_variant, h->stream);
-    else { const FusedSplit sp{h->tb_no_walkers ? nullptr : h->tb_stream, h->ev_tb_fork, h->ev_tb_join}; launch_viterbi_fused(fa, h->fplan.variant, h->fplan.n_slots, h->stream, fa.done ? &sp : nullptr); }
+    launch_plan(h, h->stream);
     mark(h, dabphy_handle::ST_MSC_VITERBI, true);
     if (fa.done) launch_copy_out(fa.done + fa.n_work + 1, h->h_tb_gave_up, sizeof(uint32_t), h->stream);
     if (h->fplan.fic_in) HIPCHK(h, hipEventRecord(h->ev_fused_done, h->stream));

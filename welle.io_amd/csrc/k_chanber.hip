@@ -35,9 +35,9 @@ __global__ void __launch_bounds__(64) k_chanber(BerArgs B)
     const FusedArgs& A = B.f;
     const int lane = threadIdx.x;
     const uint32_t wk = as_constant(A.work)[blockIdx.x >> 6];
-    const uint32_t ci = wk >> 24;
+    const uint32_t ci = work_class(wk);
     const DABPHY_CONST_AS FusedClass& C = as_constant(A.cls)[ci];
-    const int cw = (int)(wk & 0xffffffu) * 64 + (int)(blockIdx.x & 63u);
+    const int cw = (int)work_group(wk) * 64 + (int)(blockIdx.x & 63u);
     if (cw >= C.n_cw) return;
     const int nsteps = C.nsteps, nbytes = C.nbits / 8;
 

@@ -379,8 +379,8 @@ __device__ __forceinline__ void tb_consume(const FusedArgs& A, int lane)
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         const uint32_t wk = work[item];
-        const DABPHY_CONST_AS FusedClass& C = classes[wk >> 24];
-        const int g = (int)(wk & 0xffffffu);
+        const DABPHY_CONST_AS FusedClass& C = classes[work_class(wk)];
+        const int g = (int)work_group(wk);
         const int nbits = C.nbits, n_cw = C.n_cw;
         const BufRsrc dec_rs = buf_rsrc(A.dec + (size_t)dec_off[item] * 64);
         const int cw_out = g * 64 + lane;
@@ -431,8 +431,8 @@ __global__ void __launch_bounds__(64, OCC) k_viterbi_fused(FusedArgs A)
     // among many short ones, so that a scratch of the longest per work-group would be many times what all groups need -- this group's own
     // (wave-uniform base + a 32-bit lane/step offset: the stores take the scalar-base addressing mode, one VGPR instead of a 64-bit pointer)
     const BufRsrc dec_rs = buf_rsrc(A.dec + (A.dec_off ? (size_t)dec_off[item] * 64 : (size_t)blockIdx.x * A.dec_slot_cells));
-    const DABPHY_CONST_AS FusedClass& C = classes[wk >> 24];
-    const int g = (int)(wk & 0xffffffu);
+    const DABPHY_CONST_AS FusedClass& C = classes[work_class(wk)];
+    const int g = (int)work_group(wk);
     const int nsteps = C.nsteps, nbits = C.nbits, n_cw = C.n_cw, n_windows = C.n_windows;
     const long long cw0 = (long long)g * 64;
     const int cw = (int)cw0 + lane;

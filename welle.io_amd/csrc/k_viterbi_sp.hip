@@ -46,7 +46,7 @@
 
 namespace dabphy {
 
-constexpr int SP_HIST = 30;                       // trellis steps per decision history word (k_viterbi_sp)
+constexpr int SP_HIST = HIST_STEPS;               // trellis steps per decision history word (decode_work.h)
 namespace sp {
 __device__ __forceinline__ int rotl6(int x, int r) { r %= 6; return r == 0 ? x : (((x << r) | (x >> (6 - r))) & 63); }
 }
@@ -58,8 +58,8 @@ __global__ void __launch_bounds__(64, OCC) k_viterbi_sp(FusedArgs A)
     __shared__ long long s_rowoff[16];
     const int lane = threadIdx.x;
     const uint32_t wk = as_constant(A.work)[blockIdx.x >> 6];
-    const DABPHY_CONST_AS FusedClass& C = as_constant(A.cls)[wk >> 24];
-    const int cw = (int)(wk & 0xffffffu) * 64 + (int)(blockIdx.x & 63u);
+    const DABPHY_CONST_AS FusedClass& C = as_constant(A.cls)[work_class(wk)];
+    const int cw = (int)work_group(wk) * 64 + (int)(blockIdx.x & 63u);
     const int nsteps = C.nsteps, nbits = C.nbits;
     if (cw >= C.n_cw || nsteps > MAXSTEPS) return;
 

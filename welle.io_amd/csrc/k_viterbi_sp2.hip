@@ -46,7 +46,7 @@
 
 namespace dabphy {
 
-constexpr int SP2_HIST = 30;                      // trellis steps per decision history word: a multiple of the five layouts and of the six-step code word granule
+constexpr int SP2_HIST = HIST_STEPS;              // trellis steps per decision history word (decode_work.h): a multiple of the five layouts and of the six-step code word granule
 namespace sp2 {
 __device__ __forceinline__ int rotl5(int x, int r) { r %= 5; return r == 0 ? x : (((x << r) | (x >> (5 - r))) & 31); }
 __host__ __device__ constexpr int xbit(int f) { return 4 - f; }                  // lane bit of the exchange after a step in layout f
@@ -64,8 +64,8 @@ __global__ void __launch_bounds__(64, OCC) k_viterbi_sp2(FusedArgs A)
     __shared__ long long s_rowoff[2][16];
     const int lane = threadIdx.x, half = lane >> 5, j = lane & 31;
     const uint32_t wk = as_constant(A.work)[blockIdx.x >> 5];
-    const DABPHY_CONST_AS FusedClass& C = as_constant(A.cls)[wk >> 24];
-    const int cw_a = (int)(wk & 0xffffffu) * 64 + 2 * (int)(blockIdx.x & 31u);
+    const DABPHY_CONST_AS FusedClass& C = as_constant(A.cls)[work_class(wk)];
+    const int cw_a = (int)work_group(wk) * 64 + 2 * (int)(blockIdx.x & 31u);
     const int nsteps = C.nsteps;
     if (cw_a >= C.n_cw) return;
     const bool second = cw_a + 1 < C.n_cw;                                  // (an odd class: the last wave's upper half decodes the same code word again, its output is dropped)
@@ -198,8 +198,8 @@ __global__ void __launch_bounds__(64 * TB_SEG) DABPHY_WAVES_PER_SIMD(TB_SEG == 3
     __shared__ int s_again[TB_SEG];
     const int lane = threadIdx.x & 63, seg = uniform_i32((int)(threadIdx.x >> 6));
     const uint32_t wk = as_constant(A.work)[blockIdx.x];
-    const DABPHY_CONST_AS FusedClass& C = as_constant(A.cls)[wk >> 24];
-    const int cw = (int)(wk & 0xffffffu) * 64 + lane;
+    const DABPHY_CONST_AS FusedClass& C = as_constant(A.cls)[work_class(wk)];
+    const int cw = (int)work_group(wk) * 64 + lane;
     const int nsteps = C.nsteps, nbits = C.nbits;
     const bool live = cw < C.n_cw;
     if (threadIdx.x < TB_SEG) s_again[threadIdx.x] = 0;
