@@ -1,4 +1,4 @@
-"""Cases for the Reed-Solomon syndromes taken from the generator-polynomial remainder (k_rs.hip: rs_remainder120 +
+"""Cases for the Reed-Solomon syndromes taken from the generator-polynomial remainder (rs_codec.h: rs_remainder120 +
 rs_syndromes_from_remainder) and for the superframe filter's wide pass with several attempts per work-group (k_superframe_wide); run by
 tests/test_emu_rs_remainder.py on the execution model and by tests/test_gpu_rs_remainder.py on the device."""
 import functools

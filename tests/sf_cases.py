@@ -1,4 +1,4 @@
-"""Generators for the DAB+ back end's tests (k_rs.hip, dabphy_superframes.hip): superframes of every access-unit layout and bit rate
+"""Generators for the DAB+ back end's tests (k_rs.hip, k_superframe.hip, dabphy_superframes.hip): superframes of every access-unit layout and bit rate
 8 * s (s = 1 .. 48), the ways CheckSync (dabplus_decoder.cpp:171-215) rejects one, and Reed-Solomon words that walk the decoder's corner
 paths on purpose -- roots in the padding, miscorrections that are written in full, errors at the edges of the shortened code, zero
 data, S0 = 0 -- which random error patterns meet about once in ten thousand words."""

@@ -175,12 +175,7 @@ extern "C" void msc_rows_info(const dabphy_handle* h, uint32_t b, dabphy_handle:
 {
     const uint32_t F = h->last_frames;
     const auto& cls = h->classes[w.cls];
-    if (first_valid) {
-        // DabAudio emits its first logical frame on the 17th CIF it is fed (dab-audio.cpp:146-149): counted from the CIF at which this
-        // sub-channel was selected (0 for one that was there from the start of the stream)
-        const int64_t fed = 4 * h->h_desc[(size_t)b * F].frame_no - cls.pairs[w.pair].cif0;
-        *first_valid = fed >= 16 ? 0 : (int32_t)(16 - fed);
-    }
+    if (first_valid) *first_valid = (int32_t)batch_first_row(h->h_desc[(size_t)b * F].frame_no, cls.pairs[w.pair].cif0);   // (not clamped to n_rows)
     if (n_rows) {
         int nv = 0;
         for (uint32_t f = 0; f < F; f++) nv += h->h_desc[(size_t)b * F + f].valid == 1 ? 1 : 0;

@@ -110,7 +110,7 @@ struct dabphy_handle {
         DevBuf dab_run, mp2_run; int n_dab = 0, n_mp2 = 0;
         DevBuf mp2_state, mp2_snap, mp2_ev, mp2_n, mp2_err, mp2_fu;
         bool dabplus_rate() const { return (prot.nbits / 24) % 8 == 0 && prot.nbits / 8 >= 10; }
-        size_t sf_stride() const { return ((size_t)16 + 5 * (size_t)(prot.nbits / 8) + 15) & ~(size_t)15; }
+        size_t sf_stride() const { return sf_state_stride(prot.nbits / 8); }
     };
     struct PairRef { int cls = -1, pair = -1; };
     const cf32* s_iq = nullptr;       // DEVICE pointer to [B][stride] samples (caller's or s_iq_own)

@@ -2,6 +2,7 @@
 #pragma once
 #include "dabphy_common.h"
 #include "decode_work.h"
+#include "batch_rows.h"
 
 namespace dabphy {
 
@@ -372,7 +373,7 @@ void launch_resample(const ResampleArgs& a, hipStream_t s);           // the res
 void launch_copy_f4(const void* src, void* dst, size_t n16, int blocks, hipStream_t s);
 void launch_copy_out(const void* src_device, void* dst_host, size_t bytes, hipStream_t s);      // a kernel's stores into page-locked host memory (hipHostMalloc: the same address on the device)
 
-// Reed-Solomon (k_rs.hip)
+// Reed-Solomon (rs_codec.h: the code; k_rs.hip: the bare seams)
 // The code's tables as the host uploads them once per handle (dabphy_superframes.hip: ensure_gf), in one buffer: alpha_to[256] and index_of[256] of
 // GF(256) / 0x11D (init_rs.h:48-60), then the remainder table of the generator polynomial g(x) = prod (x - alpha^i), i = 0 .. 9: row f holds the ten
 // products f g_k, k = 0 .. 9, padded to 16 bytes (rs_remainder120), then the wide pass' two counters (SfArgs::wide_stats)
@@ -390,7 +391,7 @@ struct RsMscArgs {         // superframes inside a class's MSC output [n_pairs][
     int* result;                                  // [n_pairs][n_sf_per_pair][2] = corrected symbols, uncorrectable flag
     const uint8_t* gf;                            // the code's tables (above)
 };
-// DAB+ superframe filter (k_rs.hip: k_superframe): SuperframeFilter::Feed over the logical frames of one batch
+// DAB+ superframe filter (k_superframe.hip): SuperframeFilter::Feed over the logical frames of one batch
 struct SfEvent {           // = dabphy_sf_event (include/dabphy.h)
     int32_t cif, corrected, uncorrectable, sync, format, num_aus, au_start[7], au_crc_ok, sf_slot;
 };
@@ -399,7 +400,7 @@ struct SfArgs {
     const MscPair* pairs;                         // [n_pairs]
     const int32_t* run; int n_run;                // the pairs this launch walks: run[0 .. n_run) (nullptr: every pair of the class, n_run = n_pairs)
     const FrameDesc* desc; int n_frames;
-    uint8_t* state; size_t state_stride;          // [n_pairs] records: int32 frame_count (+12 pad), raw[5 * frame_bytes]
+    uint8_t* state; size_t state_stride;          // [n_pairs] records of the carried window (batch_rows.h: sf_state_*)
     SfEvent* events; int32_t* n_events;           // [n_pairs][n_cif], [n_pairs]
     uint8_t* sf; int n_slots;                     // [n_pairs][n_slots][5 * frame_bytes] corrected superframes of the synced attempts
     int32_t* stats;                               // optional [B][4]: synchronised superframes, corrected symbols, uncorrectable attempts, AUs failing their CRC
@@ -407,11 +408,13 @@ struct SfArgs {
     int32_t* accepted;                            // [n_pairs]: set by the wide pass for what it settled (nullptr: serial walk only)
     unsigned long long* wide_stats;               // [2]: pair batches the wide pass settled / was tried on
 };
-// the classes of one launch (k_rs.hip): cls = DEVICE array of n_cls argument blocks, first = DEVICE array [n_cls + 1] of first blocks
+// the classes of one launch (k_superframe.hip): cls = DEVICE array of n_cls argument blocks, first = DEVICE array [n_cls + 1] of first blocks
 // replay (k_superframe_wide only, dabphy_time_superframe_wide): the launch is a repetition of one whose pairs have been settled since -- see the kernel
 // wide_rows (k_superframe_wide only, set by its launcher): the grid rows that have work
 struct SfBatch { const SfArgs* cls; const int32_t* first; int n_cls; int replay, wide_rows; };
-inline int sf_bucket(int frame_bytes) { const int sf_len = 5 * frame_bytes; return sf_len <= 960 ? 0 : sf_len <= 2880 ? 1 : 2; }
+// the buckets of a launch: the superframe bytes (120 s) the kernels' instances hold in LDS: <= 64 / 192 / 384 kbit/s
+constexpr int SF_BUCKET_BYTES[3] = {960, 2880, 5760};
+inline int sf_bucket(int frame_bytes) { const int sf_len = 5 * frame_bytes; return sf_len <= SF_BUCKET_BYTES[0] ? 0 : sf_len <= SF_BUCKET_BYTES[1] ? 1 : 2; }
 // MP2 frame check (k_mp2.hip): MP2Decoder::Feed / CheckCRC over the logical frames of classic DAB services
 constexpr int MP2_RING = 8192;             // LDS ring of a service's byte stream
 constexpr int MP2_CARRY = 4096;            // bytes a service can carry to the next batch (what mpg123 has not consumed yet)

@@ -55,7 +55,7 @@ int prepare_superframes(dabphy_handle* h, uint32_t F)
         pairs += P; bytes += P * n_slots * 5 * (size_t)(cls.prot.nbits / 8);
         if (cls.sf_state.cap < cls.sf_stride() * P) {
             if ((r = ensure(h, cls.sf_state, cls.sf_stride() * P))) return r;
-            HIPCHK(h, hipMemsetAsync(cls.sf_state.p, 0, cls.sf_state.cap, h->stream));      // frame_count = 0: nothing collected yet
+            HIPCHK(h, hipMemsetAsync(cls.sf_state.p, 0, cls.sf_state.cap, h->stream));      // sf_state_count = 0: nothing collected yet
         }
     }
     if (!pairs) return 0;

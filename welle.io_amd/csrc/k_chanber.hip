@@ -13,7 +13,7 @@
 // lane 0 stores the pair: no atomics, no second pass, no LDS beyond locate()'s sixteen row offsets.
 //
 // An MSC code word is counted when its row is one the batch decoded (the rule of dabphy_get_msc_ensemble and of the superframe
-// filter, k_rs.hip sf_plan: rows [first_valid, n_rows) counted from MscPair::cif0); the others store {0, 0}.
+// filter, batch_rows.h: rows [first_valid, n_rows) counted from MscPair::cif0); the others store {0, 0}.
 //
 // k_chanber_totals: the batch's per-code-word counts -> per-service totals [ensemble][1 + list positions], one wavefront each.
 #include "dabphy_kernels.h"
@@ -42,13 +42,12 @@ __global__ void __launch_bounds__(64) k_chanber(BerArgs B)
     const int nsteps = C.nsteps, nbytes = C.nbits / 8;
 
     bool counted = true;
-    if (C.kind == 0) {                                                  // a row the batch decoded?  (k_rs.hip: sf_plan)
+    if (C.kind == 0) {                                                  // a row the batch decoded?  (batch_rows.h)
         const int F = A.n_frames, R = 4 * F, pair = cw / R, r = cw - pair * R;
         const MscPair pp = C.pairs[pair];
         int nv = 0;
         for (int f = 0; f < F; f++) nv += A.desc[(size_t)pp.ens * F + f].valid == 1 ? 1 : 0;
-        const long long fed = 4 * A.desc[(size_t)pp.ens * F].frame_no + r - pp.cif0;
-        counted = r < 4 * nv && fed >= 16 && pp.cif0 >= 0;
+        counted = r < 4 * nv && r >= batch_first_row(A.desc[(size_t)pp.ens * F].frame_no, pp.cif0) && pp.cif0 >= 0;
     }
     const int8_t* const base = locate(A, C, cw, lane, s_rowoff);
     __syncthreads();

@@ -247,15 +247,14 @@ __global__ void __launch_bounds__(64) k_mp2(Mp2Args A)
     const int fb = A.frame_bytes;
     Mp2State* st = reinterpret_cast<Mp2State*>(A.state + (size_t)bm * A.state_stride);
     uint8_t* carry = A.state + (size_t)bm * A.state_stride + sizeof(Mp2State);
-    // which rows of this batch the service decoded: every row (unit entry), or as the DAB+ filter counts them (k_rs.hip: sf_plan)
+    // which rows of this batch the service decoded: every row (unit entry), or as the DAB+ filter counts them (batch_rows.h)
     int r_first = 0, n_rows = A.n_cif;
     const int b = A.pairs ? A.pairs[bm].ens : 0;
     if (A.desc) {
         int nv = 0;
         for (int f = 0; f < A.n_frames; f++) nv += A.desc[(size_t)b * A.n_frames + f].valid == 1 ? 1 : 0;
-        const long long c0 = 4 * A.desc[(size_t)b * A.n_frames].frame_no;
         n_rows = 4 * nv;
-        while (r_first < n_rows && c0 + r_first - A.pairs[bm].cif0 < 16) r_first++;
+        r_first = batch_first_row(A.desc[(size_t)b * A.n_frames].frame_no, A.pairs[bm].cif0, n_rows);
     }
     const int carry_len = st->carry_len;
     const int64_t origin = st->origin;
